@@ -18,6 +18,13 @@ row for the kernel ACTUALLY selected by --kernel at the size actually run
 N=4096 on T4-class hardware) x n_gpus; the JSON's metric/model/inject
 fields likewise reflect the real flags, so a run with --kernel huge or
 --kernel rocblas is labeled as the plain kernel it measured.
+
+A plain run does only what the headline figure needs: setup, warmup, the
+--steps timed steps, the optional --dump-outputs write, the result line
+(`ms_per_step` = milliseconds per timed step).  --dump-outputs DIR saves
+the output matrix of the last timed step as float32 .npy for comparing two
+builds output for output; --full is where secondary measurements belong
+(none exist yet, so it changes nothing).
 """
 
 import argparse
@@ -56,6 +63,25 @@ def baseline_gflops_per_gpu(kernel: str, size: int):
     return None
 
 
+_DUMP_MAX_BYTES = 48 << 20  # per file; keeps a dump well under 64 MB
+
+
+def dump_output(out_dir: str, name: str, t: torch.Tensor) -> None:
+    """Write `t` as out_dir/<name>.npy in float32.  A matrix above the size
+    cap is reduced to a fixed sample of whole rows (ascending indices drawn
+    by numpy's default_rng(0)), the same rows for every run of that shape."""
+    import numpy as np
+    arr = t.detach().to("cpu", torch.float32).contiguous().numpy()
+    if arr.nbytes > _DUMP_MAX_BYTES:
+        arr = arr.reshape(arr.shape[0], -1)
+        keep = max(1, _DUMP_MAX_BYTES // (arr.shape[1] * 4))
+        rows = np.sort(np.random.default_rng(0).choice(
+            arr.shape[0], size=min(keep, arr.shape[0]), replace=False))
+        arr = arr[rows]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -75,11 +101,26 @@ def main():
                          "— the fused path is capture-safe: no syncs, "
                          "stream-ordered workspace, stream-K bypasses "
                          "itself under capture)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the output matrix of "
+                         "the LAST timed step to DIR/c.npy (float32; one "
+                         "c_rank<r>.npy per rank when multi-rank).  The "
+                         "clock is paused before that step to reset C to a "
+                         "seeded matrix, so the dump depends only on the "
+                         "arguments, not on how many steps ran before")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the benchmark's secondary measurements; "
+                         "there are none yet — a plain run already does "
+                         "only setup, warmup, the timed steps and the "
+                         "result line — so this is accepted and changes "
+                         "nothing")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     cpu_ci = args.device == "cpu"
     if not cpu_ci and not torch.cuda.is_available():
-        raise SystemExit("bench.py needs a ROCm GPU (run under gpurun)")
+        raise SystemExit("bench.py needs a ROCm GPU (or --device cpu)")
 
     from ft_sgemm_amd import ops
     from ft_sgemm_amd.parallel import init_from_env
@@ -133,6 +174,14 @@ def main():
     if args.graph and (cpu_ci or args.mode != "replicated"):
         raise SystemExit("--graph needs --device cuda --mode replicated")
 
+    # the matrix every step updates in place (a caller's result)
+    c_out = c_loc if args.mode == "blockrow" else c
+    c_seed = None
+    if args.dump_outputs:
+        # C as the last timed step finds it (drawn after a and b, so the
+        # operands are the same with and without the option)
+        c_seed = torch.rand_like(c_out) * 1.8 - 0.9
+
     warm0 = time.perf_counter()
     for _ in range(args.warmup):
         step()
@@ -168,11 +217,22 @@ def main():
             torch.cuda.synchronize()
 
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    paused = 0.0
+    if c_seed is not None:
+        # stop the clock, give the last step a known C, restart the clock
+        if not cpu_ci:
+            torch.cuda.synchronize()
+        p0 = time.perf_counter()
+        c_out.copy_(c_seed)
+        if not cpu_ci:
+            torch.cuda.synchronize()
+        paused = time.perf_counter() - p0
+    last = step()
     if not cpu_ci:
         torch.cuda.synchronize()
-    elapsed = time.perf_counter() - t0
+    elapsed = time.perf_counter() - t0 - paused
     if world > 1:
         dist.barrier()
         t = torch.tensor([elapsed], device="cpu" if cpu_ci else dev)
@@ -187,6 +247,12 @@ def main():
     mult = 1 if args.mode == "blockrow" else world
     agg_gflops = mult * flop_per_step * args.steps / elapsed / 1e9
     ms_per_step = elapsed / args.steps * 1e3
+
+    if args.dump_outputs:
+        # the CPU replicated step returns its product instead of updating C
+        out = last if cpu_ci and args.mode == "replicated" else c_out
+        dump_output(args.dump_outputs,
+                    "c" if world == 1 else f"c_rank{rank}", out)
 
     if rank == 0:
         metric, model, inject, faults = _KERNEL_META[args.kernel]

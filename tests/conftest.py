@@ -1,5 +1,14 @@
+import os
+import sys
+
 import pytest
 import torch
+
+# the package and bench.py are imported from the repository tree, whichever
+# directory or launcher (`pytest` / `python -m pytest`) starts the suite
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if _ROOT not in sys.path:
+    sys.path.insert(0, _ROOT)
 
 
 def pytest_configure(config):
