@@ -157,15 +157,8 @@ __global__ __launch_bounds__(256) void segsum_kernel(
   }
 }
 
-// NTC: non-temporal C epilogue loads/stores (beta != 0 streams 2x64 MB of C
-// through the caches per GEMM at N=4096 — nt keeps it from evicting the
-// L3-resident A/B panels).  SWIZ: bijective XCD-aware blockIdx remap.
-// PIPE=1 (plain kernels only): 3-LDS-buffer glds ring with raw s_barrier +
-// counted s_waitcnt — panels it+1 and it+2 stay in flight across the
-// barrier instead of draining at every __syncthreads.
 template <int BM, int BN, int BK, int WM, int WN, int MM, bool ABFT,
-          bool INJECT, bool NTC = false, bool SWIZ = false, int OCC = 2,
-          int PIPE = 0>
+          bool INJECT, int OCC = 2>
 __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
     int M, int N, int K, const float* __restrict__ A,
     const float* __restrict__ B, float* __restrict__ C, float alpha,
@@ -183,12 +176,8 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
   // saw(64)] window of the precomputed segment sums, streamed by
   // global_load_lds.  Only A-side sums are needed: the column checksums
   // detect, the weighted ones locate the row, and the column is lane-local.
-  static_assert(!(ABFT && PIPE) && !(INJECT && PIPE),
-                "3-buffer ring is plain-only");
-  constexpr int NBUF = PIPE ? 3 : 2;
-  constexpr int STRIP_OFF = NBUF * BUF;
-  constexpr int LDS_FLOATS = ABFT ? (STRIP_OFF + NWAVES * 256)
-                                  : (NBUF * BUF);
+  constexpr int STRIP_OFF = 2 * BUF;
+  constexpr int LDS_FLOATS = ABFT ? (STRIP_OFF + NWAVES * 256) : (2 * BUF);
 
   __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
 
@@ -199,20 +188,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
   const int wm_idx = wave / WAVES_N, wn_idx = wave % WAVES_N;
   const int wi0 = wm_idx * WM;
   const int wj0 = wn_idx * WN;
-  int bx = blockIdx.x, by = blockIdx.y;
-  if constexpr (SWIZ) {
-    // bijective XCD remap: consecutive remapped ids land on one XCD so
-    // each XCD's L2 sees a contiguous band of output tiles.
-    const int nwg = gridDim.x * gridDim.y;
-    const int orig = by * gridDim.x + bx;
-    const int qq = nwg / 8, rr = nwg % 8;
-    const int xcd = orig % 8;
-    const int wgid =
-        (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) +
-        orig / 8;
-    bx = wgid % gridDim.x;
-    by = wgid / gridDim.x;
-  }
+  const int bx = blockIdx.x, by = blockIdx.y;
   const int im0 = bx * BM;
   const int jn0 = by * BN;
 
@@ -418,52 +394,13 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
   // buffered by strip-window parity.
   constexpr int PPS = 64 / BK;  // panels per strip window (BK <= 64)
   static_assert(64 % BK == 0 || !ABFT, "ABFT needs BK dividing 64");
-  constexpr int GLD = GA + GB;  // glds instructions per panel
   stage(0, 0);
   if constexpr (ABFT) strip_stage(0, 0);  // window (panels 0..PPS-1)
   FT_PARA_SYNC();
-  if constexpr (PIPE) {
-    // 3-buffer ring: prologue stages two panels; the main loop keeps the
-    // newest one in flight across each barrier.
-    if (BK < K) stage(1, BK);
-  }
-  if constexpr (!PIPE) __syncthreads();  // drains in-flight glds
+  __syncthreads();  // drains in-flight glds
 
   const int niter = K / BK;
-  if constexpr (PIPE) {
-    for (int it = 0; it < niter; ++it) {
-      const int q = it % 3;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();  // readers of buf (it+2)%3 are done
-      if (it + 2 < niter) {
-        stage((it + 2) % 3, (it + 2) * BK);
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * GLD) : "memory");
-      } else if (it + 1 < niter) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GLD) : "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      const float* As = &lds[q * BUF];
-      const float* Bs = &lds[q * BUF + BM * BK];
-#pragma unroll
-      for (int kk = 0; kk < BK / KSTEP; ++kk) {
-        const int kloc = kk * KSTEP + sub;
-        float a[FM], b[FN];
-#pragma unroll
-        for (int fm = 0; fm < FM; ++fm)
-          a[fm] = As[kloc * BM + wi0 + fm * MM + r];
-#pragma unroll
-        for (int fn = 0; fn < FN; ++fn)
-          b[fn] = Bs[kloc * BN + wj0 + fn * MM + r];
-#pragma unroll
-        for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-          for (int fn = 0; fn < FN; ++fn)
-            acc[fm][fn] = T::mma(a[fm], b[fn], acc[fm][fn]);
-      }
-    }
-  }
-  int it = PIPE ? niter : 0;  // PIPE path already done; skip burst loop
+  int it = 0;
   while (it < niter) {
     if constexpr (INJECT) {
       // Deterministic rotating injector, once per verify window (reference:
@@ -527,7 +464,6 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
       __syncthreads();
     }
     if constexpr (ABFT) verify_correct();
-    if constexpr (!ABFT && !INJECT) { /* plain: single burst, no verify */ }
   }
 
   // ---- epilogue: alpha/beta merge, float4 along column-major columns ----
@@ -542,8 +478,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
         float* p = colbase + 4 * sub + 8 * g;
         f32x4 out;
         if (beta != 0.f) {
-          const f32x4 prev = NTC ? __builtin_nontemporal_load((const f32x4*)p)
-                                 : *(const f32x4*)p;
+          const f32x4 prev = *(const f32x4*)p;
 #pragma unroll
           for (int u = 0; u < 4; ++u)
             out[u] = alpha * acc[fm][fn][4 * g + u] + beta * prev[u];
@@ -551,10 +486,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
 #pragma unroll
           for (int u = 0; u < 4; ++u) out[u] = alpha * acc[fm][fn][4 * g + u];
         }
-        if constexpr (NTC)
-          __builtin_nontemporal_store(out, (f32x4*)p);
-        else
-          *(f32x4*)p = out;
+        *(f32x4*)p = out;
       }
     }
 }

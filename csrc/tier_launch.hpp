@@ -35,7 +35,31 @@ inline int streamk_env_mode() {
   return e ? std::atoi(e) : 2;
 }
 
-inline int abft_sstr(int K);  // defined below
+// ABFT workspace layout: (M/WM) rows, one per WM-band of A, each of
+// 2 * sstr floats holding the (plain, row-weighted) segment-sum pairs
+// INTERLEAVED at [2k], [2k+1]; sstr = round_up(K, 64) so the fused
+// kernel's 64-k strip loads never cross rows.  B-side sums are not needed
+// by the ratio-locate scheme.
+inline int abft_sstr(int K) { return (K + 63) & ~63; }
+
+template <int WM, int WN>
+size_t abft_workspace_floats_t(int M, int N, int K) {
+  return 2 * (size_t)(M / WM) * abft_sstr(K);
+}
+
+// ABFT encode: precompute the plain + row-weighted segment checksums of A
+// (per WM-row band) into ws: one coalesced pass over the operand, ~1-2% of
+// the GEMM at N=4096 (vs -11.6% for the in-kernel cooperative sums pass
+// this replaces — tools/probe_ablate.hip).  Returns the row stride sstr
+// the fused kernel reads ws with.
+template <int WM>
+int abft_encode(int M, int K, const float* A, float* ws, hipStream_t stream) {
+  const int sstr = abft_sstr(K);
+  RoctxRange rr("abft_encode_segsum");
+  hipLaunchKernelGGL((segsum_kernel<WM>), dim3(K), dim3(256), 0, stream, M,
+                     K, sstr, A, ws);
+  return sstr;
+}
 
 inline int device_cu_count() {
   static int cus = [] {
@@ -64,19 +88,16 @@ hipError_t launch_tier_streamk_t(bool abft, bool inject, int M, int N, int K,
     return hipErrorNotSupported;
   constexpr int THREADS = 64 * (BM / WM) * (BN / WN);
 
-  const void* kfn;
-  if (abft && inject)
-    kfn = (const void*)&sgemm_mfma_streamk<BM, BN, BKF, WM, WN, MM, true,
-                                           true>;
-  else if (abft)
-    kfn = (const void*)&sgemm_mfma_streamk<BM, BN, BKF, WM, WN, MM, true,
-                                           false>;
-  else
-    kfn = (const void*)&sgemm_mfma_streamk<BM, BN, BK, WM, WN, MM, false,
-                                           false>;
+  // the three variants share one signature: select once, for both the
+  // occupancy query and the launch
+  const auto kfn =
+      abft ? (inject ? &sgemm_mfma_streamk<BM, BN, BKF, WM, WN, MM, true, true>
+                     : &sgemm_mfma_streamk<BM, BN, BKF, WM, WN, MM, true,
+                                           false>)
+           : &sgemm_mfma_streamk<BM, BN, BK, WM, WN, MM, false, false>;
   int maxblk = 0;
-  const hipError_t oe =
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&maxblk, kfn, THREADS, 0);
+  const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+      &maxblk, (const void*)kfn, THREADS, 0);
   const bool dbg = std::getenv("FT_SGEMM_SK_DEBUG") != nullptr;
   if (oe != hipSuccess || maxblk < 1) {
     if (dbg)
@@ -138,10 +159,7 @@ hipError_t launch_tier_streamk_t(bool abft, bool inject, int M, int N, int K,
   int sstr = 0;
   if (abft) {
     if (!ws) return hipErrorInvalidValue;
-    sstr = abft_sstr(K);
-    RoctxRange rr("abft_encode_segsum");
-    hipLaunchKernelGGL((segsum_kernel<WM>), dim3(K), dim3(256), 0, stream, M,
-                       K, sstr, A, ws);
+    sstr = abft_encode<WM>(M, K, A, ws, stream);
     SA = ws;
   }
   RoctxRange rr_main(abft ? (inject ? "ft_sgemm_streamk_abft_inject"
@@ -177,22 +195,8 @@ hipError_t launch_tier_streamk_t(bool abft, bool inject, int M, int N, int K,
   if (hipMallocAsync((void**)&partials, pbytes, stream) != hipSuccess)
     return hipErrorNotSupported;  // nothing mutated yet; classic path
 
-  if (abft && inject) {
-    hipLaunchKernelGGL(
-        (sgemm_mfma_streamk<BM, BN, BKF, WM, WN, MM, true, true>), dim3(G),
-        dim3(THREADS), 0, stream, M, N, K, A, B, C, alpha, beta, istride,
-        tau, inj_mag, SA, sstr, partials);
-  } else if (abft) {
-    hipLaunchKernelGGL(
-        (sgemm_mfma_streamk<BM, BN, BKF, WM, WN, MM, true, false>), dim3(G),
-        dim3(THREADS), 0, stream, M, N, K, A, B, C, alpha, beta, istride,
-        tau, inj_mag, SA, sstr, partials);
-  } else {
-    hipLaunchKernelGGL(
-        (sgemm_mfma_streamk<BM, BN, BK, WM, WN, MM, false, false>), dim3(G),
-        dim3(THREADS), 0, stream, M, N, K, A, B, C, alpha, beta, istride,
-        tau, inj_mag, SA, sstr, partials);
-  }
+  hipLaunchKernelGGL(kfn, dim3(G), dim3(THREADS), 0, stream, M, N, K, A, B, C,
+                     alpha, beta, istride, tau, inj_mag, SA, sstr, partials);
   hipError_t err = hipGetLastError();
   if (err == hipSuccess) {
     // combine split tiles (fully-owned tiles exit immediately)
@@ -203,20 +207,6 @@ hipError_t launch_tier_streamk_t(bool abft, bool inject, int M, int N, int K,
   }
   (void)hipFreeAsync(partials, stream);
   return err;
-}
-
-// ABFT workspace layout: (M/WM) rows, one per WM-band of A, each of
-// 2 * sstr floats holding the (plain, row-weighted) segment-sum pairs
-// INTERLEAVED at [2k], [2k+1]; sstr = round_up(K, 64) so the fused
-// kernel's 64-k strip loads never cross rows.  B-side sums are not needed
-// by the ratio-locate scheme.
-inline int abft_sstr(int K) { return (K + 63) & ~63; }
-
-template <int WM, int WN>
-size_t abft_workspace_floats_t(int M, int N, int K) {
-  // plain + row-weighted A-segment sums (B-side sums are not needed by the
-  // ratio-locate scheme)
-  return 2 * (size_t)(M / WM) * abft_sstr(K);
 }
 
 // BKF: K-panel depth of the fused-ABFT twin (may be smaller than the
@@ -242,15 +232,8 @@ hipError_t launch_tier(bool abft, bool inject, int M, int N, int K,
   const float* SA = nullptr;
   int sstr = 0;
   if (abft) {
-    // Precompute the plain + row-weighted segment checksums of A (per
-    // WM-row band): one coalesced pass over the operand, ~1-2% of the GEMM
-    // at N=4096 (vs -11.6% for the in-kernel cooperative sums pass this
-    // replaces — tools/probe_ablate.hip).
     if (!ws) return hipErrorInvalidValue;
-    sstr = abft_sstr(K);
-    RoctxRange rr("abft_encode_segsum");
-    hipLaunchKernelGGL((segsum_kernel<WM>), dim3(K), dim3(256), 0, stream, M,
-                       K, sstr, A, ws);
+    sstr = abft_encode<WM>(M, K, A, ws, stream);
     SA = ws;
   }
   RoctxRange rr_main(abft ? (inject ? "ft_sgemm_abft_inject" : "ft_sgemm_abft")

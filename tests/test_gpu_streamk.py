@@ -71,8 +71,9 @@ def test_streamk_fused_inject(tier, shape):
 
 
 def test_streamk_beta_prescale():
-    """beta is applied by the one-pass prescale kernel exactly once, then
-    split tiles accumulate atomically."""
+    """beta is applied exactly once per output element: by the direct
+    epilogue for tiles one workgroup owns fully, by sk_fixup_kernel (after
+    it has summed the raw partial slots) for split tiles."""
     m = n = k = 1024
     a, b, c = ops.make_operands(m, n, k)
     c.normal_()
@@ -124,6 +125,32 @@ def test_streamk_multi_segment_workgroups(g):
         a, b, c = ops.make_operands(m, n, k)
         ref = ops.torch_reference(a, b, c, 1.0, 0.0)
         ops.ft_sgemm("huge", a, b, c, 1.0, 0.0, inject=True)
+        torch.cuda.synchronize()
+        check(ref, c)
+    finally:
+        os.environ.pop("FT_SGEMM_SK_G", None)
+
+
+@pytest.mark.parametrize("tier", ["huge", "large"])
+def test_streamk_beta_all_epilogue_paths(tier):
+    """beta != 0 through every path that writes C, on both stream-K tiers.
+    (512, 384, 640) divides both tiles and is 10 units per tile; G=7 gives
+    every workgroup a head partial, fully-owned tiles and a tail partial
+    (huge: 60 units in ranges of 9/9/9/9/8/8/8; large: 480 units in
+    69/69/69/69/68/68/68), so the direct epilogue, both fixup slots and
+    the fixup's g0 == gl early-out all run with C pre-filled."""
+    os.environ["FT_SGEMM_SK_G"] = "7"
+    try:
+        m, n, k = 512, 384, 640
+        a, b, c = ops.make_operands(m, n, k)
+        c.normal_()
+        c0 = c.clone()
+        ref = ops.torch_reference(a, b, c0, 1.0, -1.5)
+        ops.sgemm(tier, a, b, c, 1.0, -1.5)
+        torch.cuda.synchronize()
+        check(ref, c)
+        c.copy_(c0)
+        ops.ft_sgemm(tier, a, b, c, 1.0, -1.5, inject=True)
         torch.cuda.synchronize()
         check(ref, c)
     finally:

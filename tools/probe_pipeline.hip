@@ -256,30 +256,35 @@ __global__ void max_diff(const float* x, const float* y, size_t n,
 
 // Library-kernel tile/wave-shape variants (plain or fused-ABFT+inject).
 template <int BM_, int BN_, int BK_, int WM_, int WN_, bool ABFT_ = false,
-          bool INJ_ = false, bool NTC_ = false, bool SWIZ_ = false,
-          int BETA10 = 0, int MM_ = 32, int OCC_ = 2, int PIPE_ = 0>
+          bool INJ_ = false, int BETA10 = 0, int MM_ = 32, int OCC_ = 2>
 static void run_lib(const char* name, int n, const float* dA, const float* dB,
                     float* dC, const float* dRef, float* dMax, int reps) {
   const float beta_ = BETA10 / 10.f;
   dim3 grid(n / BM_, n / BN_), block(64 * (BM_ / WM_) * (BN_ / WN_));
-  static float* ws = nullptr;
+  // ABFT workspace: (n/WM_) rows of 2*sstr interleaved (plain, weighted)
+  // segment sums
+  float* ws = nullptr;
   const int sstr = (n + 63) & ~63;
-  if (ABFT_ && !ws) hipMalloc(&ws, 2 * (size_t)(8192 / 64) * 8192 * 4);
+  if (ABFT_ &&
+      hipMalloc(&ws, 2 * (size_t)(n / WM_) * sstr * sizeof(float)) !=
+          hipSuccess) {
+    printf("N=%d %-34s workspace hipMalloc failed\n", n, name);
+    return;
+  }
   const int niter = n / BK_, stride = niter / 20 > 0 ? niter / 20 : 1;
   auto launch = [&]() {
     if (ABFT_) {
       hipLaunchKernelGGL((ftsgemm::segsum_kernel<WM_>), dim3(n), dim3(256),
-                         0, 0, n, n, sstr, dA, ws,
-                         ws + (size_t)(n / WM_) * sstr);
+                         0, 0, n, n, sstr, dA, ws);
       hipLaunchKernelGGL(
           (ftsgemm::sgemm_mfma<BM_, BN_, BK_, WM_, WN_, MM_, ABFT_, INJ_,
-                               NTC_, SWIZ_, OCC_>),
+                               OCC_>),
           grid, block, 0, 0, n, n, n, dA, dB, dC, 1.f, beta_, stride, stride,
           9500.f, 10000.f, ws, sstr);
     } else {
       hipLaunchKernelGGL(
           (ftsgemm::sgemm_mfma<BM_, BN_, BK_, WM_, WN_, MM_, false, false,
-                               NTC_, SWIZ_, OCC_, PIPE_>),
+                               OCC_>),
           grid, block, 0, 0, n, n, n, dA, dB, dC, 1.f, beta_, stride, stride,
           1e30f, 0.f, nullptr, 0);
     }
@@ -308,6 +313,7 @@ static void run_lib(const char* name, int n, const float* dA, const float* dB,
   printf("N=%d %-34s %8.0f GFLOPS  (maxdiff %.2e) err=%s\n", n, name, gf, md,
          hipGetErrorString(hipGetLastError()));
   fflush(stdout);
+  if (ws) hipFree(ws);
 }
 
 template <int BK, int STRUCT, bool SWIZ, bool PRIO = false>
@@ -381,73 +387,73 @@ int main(int argc, char** argv) {
       }
       if (only && *only == 'T') {
         // tier tuning: tall / wide / large variants (beta=-1.5)
-        run_lib<128, 32, 32, 64, 32, false, false, false, false, -15>(
+        run_lib<128, 32, 32, 64, 32, false, false, -15>(
             "tall    bk32 plain (shipped)", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<128, 32, 16, 64, 32, false, false, false, false, -15>(
+        run_lib<128, 32, 16, 64, 32, false, false, -15>(
             "tall    bk16 plain", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<128, 32, 32, 64, 32, true, true, false, false, -15>(
+        run_lib<128, 32, 32, 64, 32, true, true, -15>(
             "tall    bk32 abft+inj (shipped)", n, dA, dB, dC, dRef, dMax,
             reps);
-        run_lib<128, 32, 16, 64, 32, true, true, false, false, -15>(
+        run_lib<128, 32, 16, 64, 32, true, true, -15>(
             "tall    bk16 abft+inj", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<128, 32, 16, 128, 32, true, true, false, false, -15>(
+        run_lib<128, 32, 16, 128, 32, true, true, -15>(
             "tall    bk16 w1 WM128 abft+inj", n, dA, dB, dC, dRef, dMax,
             reps);
-        run_lib<32, 128, 32, 32, 64, false, false, false, false, -15>(
+        run_lib<32, 128, 32, 32, 64, false, false, -15>(
             "wide    bk32 plain (shipped)", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<32, 128, 16, 32, 64, false, false, false, false, -15>(
+        run_lib<32, 128, 16, 32, 64, false, false, -15>(
             "wide    bk16 plain", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<32, 128, 16, 32, 64, true, true, false, false, -15>(
+        run_lib<32, 128, 16, 32, 64, true, true, -15>(
             "wide    bk16 abft+inj", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<32, 128, 16, 32, 128, true, true, false, false, -15>(
+        run_lib<32, 128, 16, 32, 128, true, true, -15>(
             "wide    bk16 w1 WN128 abft+inj", n, dA, dB, dC, dRef, dMax,
             reps);
-        run_lib<64, 64, 32, 64, 64, false, false, false, false, -15>(
+        run_lib<64, 64, 32, 64, 64, false, false, -15>(
             "large   bk32 plain (shipped)", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<64, 64, 16, 64, 64, false, false, false, false, -15>(
+        run_lib<64, 64, 16, 64, 64, false, false, -15>(
             "large   bk16 plain", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<64, 64, 16, 64, 64, false, false, false, false, -15, 32, 4>(
+        run_lib<64, 64, 16, 64, 64, false, false, -15, 32, 4>(
             "large   bk16 occ4 plain", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<64, 64, 16, 64, 64, true, true, false, false, -15>(
+        run_lib<64, 64, 16, 64, 64, true, true, -15>(
             "large   bk16 abft+inj", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<64, 64, 32, 64, 64, true, true, false, false, -15>(
+        run_lib<64, 64, 32, 64, 64, true, true, -15>(
             "large   bk32 abft+inj (shipped)", n, dA, dB, dC, dRef, dMax,
             reps);
-        run_lib<32, 32, 16, 32, 32, false, false, false, false, -15>(
+        run_lib<32, 32, 16, 32, 32, false, false, -15>(
             "medium  bk16 plain", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<32, 32, 16, 32, 32, true, true, false, false, -15>(
+        run_lib<32, 32, 16, 32, 32, true, true, -15>(
             "medium  bk16 abft+inj", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<128, 32, 16, 64, 32, true, true, false, false, -15, 32, 3>(
+        run_lib<128, 32, 16, 64, 32, true, true, -15, 32, 3>(
             "tall    bk16 abft+inj OCC3", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<128, 32, 16, 64, 32, true, true, false, false, -15, 32, 4>(
+        run_lib<128, 32, 16, 64, 32, true, true, -15, 32, 4>(
             "tall    bk16 abft+inj OCC4", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<32, 128, 16, 32, 64, true, true, false, false, -15, 32, 3>(
+        run_lib<32, 128, 16, 32, 64, true, true, -15, 32, 3>(
             "wide    bk16 abft+inj OCC3", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<32, 128, 16, 32, 64, true, true, false, false, -15, 32, 4>(
+        run_lib<32, 128, 16, 32, 64, true, true, -15, 32, 4>(
             "wide    bk16 abft+inj OCC4", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<64, 64, 16, 64, 64, true, true, false, false, -15, 32, 3>(
+        run_lib<64, 64, 16, 64, 64, true, true, -15, 32, 3>(
             "large   bk16 abft+inj OCC3", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<32, 32, 16, 32, 32, true, true, false, false, -15, 32, 4>(
+        run_lib<32, 32, 16, 32, 32, true, true, -15, 32, 4>(
             "medium  bk16 abft+inj OCC4", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<64, 64, 16, 32, 64, false, false, false, false, -15>(
+        run_lib<64, 64, 16, 32, 64, false, false, -15>(
             "large   bk16 w2 WM32xWN64 plain", n, dA, dB, dC, dRef, dMax,
             reps);
-        run_lib<64, 64, 16, 32, 64, true, true, false, false, -15>(
+        run_lib<64, 64, 16, 32, 64, true, true, -15>(
             "large   bk16 w2 WM32xWN64 abft+inj", n, dA, dB, dC, dRef, dMax,
             reps);
-        run_lib<256, 128, 16, 128, 64, true, true, false, false, -15>(
+        run_lib<256, 128, 16, 128, 64, true, true, -15>(
             "huge    bk16 abft+inj (enc-asm)", n, dA, dB, dC, dRef, dMax,
             reps);
-        run_lib<256, 128, 16, 128, 64, false, false, false, false, -15>(
+        run_lib<256, 128, 16, 128, 64, false, false, -15>(
             "huge    bk16 plain", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<128, 64, 16, 64, 64, false, false, false, false, -15>(
+        run_lib<128, 64, 16, 64, 64, false, false, -15>(
             "tall2   128x64x16 w2 plain", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<128, 64, 16, 64, 64, true, true, false, false, -15>(
+        run_lib<128, 64, 16, 64, 64, true, true, -15>(
             "tall2   128x64x16 w2 abft+inj", n, dA, dB, dC, dRef, dMax,
             reps);
-        run_lib<64, 128, 16, 64, 64, false, false, false, false, -15>(
+        run_lib<64, 128, 16, 64, 64, false, false, -15>(
             "wide2   64x128x16 w2 plain", n, dA, dB, dC, dRef, dMax, reps);
-        run_lib<64, 128, 16, 64, 64, true, true, false, false, -15>(
+        run_lib<64, 128, 16, 64, 64, true, true, -15>(
             "wide2   64x128x16 w2 abft+inj", n, dA, dB, dC, dRef, dMax,
             reps);
         continue;
@@ -513,43 +519,24 @@ int main(int argc, char** argv) {
           reps);
       run_lib<256, 128, 16, 64, 64>("A3p plain  256x128x16 w8 WM64xWN64", n,
                                     dA, dB, dC, dRef, dMax, reps);
-      // beta = -1.5 family (C read-modify-write traffic): NTC / SWIZ
-      run_lib<256, 128, 16, 128, 64, false, false, false, false, -15>(
+      // beta = -1.5 family (C read-modify-write traffic)
+      run_lib<256, 128, 16, 128, 64, false, false, -15>(
           "B0 plain b-1.5 base", n, dA, dB, dC, dRef, dMax, reps);
-      run_lib<256, 128, 16, 128, 64, false, false, true, false, -15>(
-          "B1 plain b-1.5 +NTC", n, dA, dB, dC, dRef, dMax, reps);
-      run_lib<256, 128, 16, 128, 64, false, false, false, true, -15>(
-          "B2 plain b-1.5 +SWIZ", n, dA, dB, dC, dRef, dMax, reps);
-      run_lib<256, 128, 16, 128, 64, false, false, true, true, -15>(
-          "B3 plain b-1.5 +NTC+SWIZ", n, dA, dB, dC, dRef, dMax, reps);
-      run_lib<256, 128, 16, 128, 64, true, true, true, true, -15>(
-          "B4 abft+inj b-1.5 +NTC+SWIZ", n, dA, dB, dC, dRef, dMax, reps);
-      run_lib<256, 128, 16, 128, 64, true, true, false, false, -15>(
+      run_lib<256, 128, 16, 128, 64, true, true, -15>(
           "B5 abft+inj b-1.5 base", n, dA, dB, dC, dRef, dMax, reps);
-      run_lib<256, 128, 16, 128, 64, false, false, true, true, 0>(
-          "B6 plain b0 +NTC+SWIZ", n, dA, dB, dC, dRef, dMax, reps);
-      run_lib<256, 128, 16, 128, 64, false, false, false, false, -15, 16>(
+      run_lib<256, 128, 16, 128, 64, false, false, -15, 16>(
           "C1 plain b-1.5 MM16 (16x16x4)", n, dA, dB, dC, dRef, dMax, reps);
-      run_lib<256, 128, 16, 128, 64, false, false, false, false, -15, 32, 3>(
+      run_lib<256, 128, 16, 128, 64, false, false, -15, 32, 3>(
           "C2 plain b-1.5 bk16 OCC3", n, dA, dB, dC, dRef, dMax, reps);
-      run_lib<256, 128, 8, 128, 64, false, false, false, false, -15, 32, 3>(
+      run_lib<256, 128, 8, 128, 64, false, false, -15, 32, 3>(
           "C3 plain b-1.5 bk8 OCC3", n, dA, dB, dC, dRef, dMax, reps);
-      run_lib<256, 128, 8, 128, 64, false, false, false, false, -15, 32, 2>(
+      run_lib<256, 128, 8, 128, 64, false, false, -15, 32, 2>(
           "C4 plain b-1.5 bk8 OCC2", n, dA, dB, dC, dRef, dMax, reps);
-      run_lib<128, 128, 16, 128, 64, false, false, false, false, -15, 32, 4>(
+      run_lib<128, 128, 16, 128, 64, false, false, -15, 32, 4>(
           "C5 plain b-1.5 128x128x16 w2 OCC4", n, dA, dB, dC, dRef, dMax,
           reps);
-      run_lib<256, 128, 16, 128, 64, true, true, false, false, -15, 32, 3>(
+      run_lib<256, 128, 16, 128, 64, true, true, -15, 32, 3>(
           "C6 abft+inj b-1.5 bk16 OCC3", n, dA, dB, dC, dRef, dMax, reps);
-      run_lib<256, 128, 16, 128, 64, false, false, false, false, -15, 32, 2,
-              1>("E1 plain b-1.5 bk16 3buf-ring", n, dA, dB, dC, dRef, dMax,
-                 reps);
-      run_lib<256, 128, 8, 128, 64, false, false, false, false, -15, 32, 2,
-              1>("E2 plain b-1.5 bk8 3buf-ring", n, dA, dB, dC, dRef, dMax,
-                 reps);
-      run_lib<256, 128, 32, 64, 128, false, false, false, false, -15, 32, 2,
-              1>("E3 plain b-1.5 bk32 3buf-ring w4 WM64WN128", n, dA, dB,
-                 dC, dRef, dMax, reps);
     }
     hipFree(dA); hipFree(dB); hipFree(dC); hipFree(dRef); hipFree(dMax);
   }
