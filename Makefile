@@ -13,10 +13,11 @@ cli: bin/ft_sgemm
 # filter out PyTorch-hipify byproducts (kernel_*_hip.hip copies)
 KERNEL_TUS := $(filter-out %_hip.hip, $(wildcard csrc/generated/kernel_*.hip))
 
-bin/ft_sgemm: csrc/cli_main.hip csrc/dispatch.hip csrc/rocblas_path.hip csrc/ft_kernels.hpp csrc/tier_launch.hpp csrc/ft_core.h csrc/generated/tile_params.h $(KERNEL_TUS)
+bin/ft_sgemm: csrc/cli_main.hip csrc/dispatch.hip csrc/rocblas_path.hip csrc/locate_selftest.hip csrc/ft_kernels.hpp csrc/ft_streamk.hpp csrc/tier_launch.hpp csrc/ft_core.h csrc/generated/tile_params.h $(KERNEL_TUS)
 	mkdir -p bin
 	$(HIPCC) -x hip --offload-arch=$(ARCH) -O3 -std=c++17 -Icsrc $(FTFLAGS) \
-	  csrc/cli_main.hip csrc/dispatch.hip csrc/rocblas_path.hip $(KERNEL_TUS) \
+	  csrc/cli_main.hip csrc/dispatch.hip csrc/rocblas_path.hip \
+	  csrc/locate_selftest.hip $(KERNEL_TUS) \
 	  -L$(ROCM)/lib -lrocblas -lroctx64 -o $@
 
 # Paranoid-sync build for the race check (tools/race_check.sh): every
@@ -26,7 +27,8 @@ bin/ft_sgemm: csrc/cli_main.hip csrc/dispatch.hip csrc/rocblas_path.hip csrc/ft_
 cli-paranoid:
 	mkdir -p bin
 	$(HIPCC) -x hip --offload-arch=$(ARCH) -O3 -std=c++17 -Icsrc -DFT_PARANOID \
-	  csrc/cli_main.hip csrc/dispatch.hip csrc/rocblas_path.hip $(KERNEL_TUS) \
+	  csrc/cli_main.hip csrc/dispatch.hip csrc/rocblas_path.hip \
+	  csrc/locate_selftest.hip $(KERNEL_TUS) \
 	  -L$(ROCM)/lib -lrocblas -lroctx64 -o bin/ft_sgemm_paranoid
 
 ext:

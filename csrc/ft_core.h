@@ -22,6 +22,18 @@ bool sgemm_tier_supported(int tier, int M, int N, int K);
 
 size_t sgemm_abft_workspace_floats(int tier, int M, int N, int K);
 
+// Device self-test of the fused kernels' shared locate/correct
+// (locate_selftest.hip): one single-wave block per case plants up to two
+// accumulator faults in a synthetic FM x FN fragment tile of MM-wide MFMA
+// fragments and corrects it with both the shipped function and the
+// sweep-everything reference form.  idesc: 9 ints per case {nfault,
+// (fm, fn, reg, lane) x 2}; fdesc: 3 floats per case {mag0, mag1, tau};
+// out: [3][ncases][FM*FN*NREG][64] floats = {shipped, reference, clean}.
+// All pointers are device pointers; (fm, fn, mm) must be a tier's shape.
+hipError_t locate_selftest_launch(int fm, int fn, int mm, int ncases,
+                                  const int* idesc, const float* fdesc,
+                                  float amp, float* out, hipStream_t stream);
+
 // rocBLAS paths (kernel id 0 oracle and the id-10 non-fused ABFT baseline,
 // reference: cuBLAS at sgemm.cu:108 / include/baseline_ft_sgemm.cuh).
 // Implemented in rocblas_path.hip.

@@ -115,6 +115,101 @@ __device__ constexpr int acc_row(int reg, int sub) {
   return (reg & 3) + 8 * (reg >> 2) + 4 * sub;
 }
 
+// ABFT ratio locate + in-register correct of one wave tile, shared by the
+// classic and the stream-K kernel (entered only after the cheap detect in
+// their verify_correct tripped; the scheme itself is described there).
+// acc[FM][FN] is the wave's accumulator tile, cc/cw this lane's plain and
+// row-weighted column-checksum partials, sub = lane / MM.
+//
+// Only the work a fault needs is done:
+//   * per fn, an fp32 SCREEN of the column residual (|rc32| > tau/2 in any
+//     lane, wave-uniform) decides whether the fragment column is looked at
+//     at all.  The exact decision below is |rc| > tau on the fp64 sum; the
+//     two residuals differ by the fp32 rounding of FM*NREG terms (~1e-2 at
+//     the |acc| ~ 1e4 of a faulty column), orders of magnitude below the
+//     tau/2 margin, so the screen passes a strict superset.
+//   * per fm, the correction sweep runs only for a fragment some lane
+//     located its row in.
+// The arithmetic on a column that IS processed is the unscreened one, in
+// the same order, so outputs are bit-identical to sweeping everything.
+template <int FM, int FN, int MM>
+__device__ __attribute__((always_inline)) inline void locate_correct(
+    typename mfma_traits<MM>::acc_t (&acc)[FM][FN], const float (&cc)[FN],
+    const float (&cw)[FN], int sub, float tau) {
+  constexpr int NREG = mfma_traits<MM>::nreg;
+#pragma unroll
+  for (int fn = 0; fn < FN; ++fn) {
+    // fp32 screen: four independent chains (order is free here — the sum
+    // only gates the branch, it never reaches the output)
+    // With a single fragment column (FN == 1) the tripped detect already
+    // says the fault is in it: no screen (it would only add code — and on
+    // the tall tier two VGPRs that cost a wave of occupancy).
+    if constexpr (FN > 1) {
+      float p[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+        for (int reg = 0; reg < NREG; ++reg) p[reg & 3] += acc[fm][fn][reg];
+      const float rc32 = slice_sum<MM>((p[0] + p[1]) + (p[2] + p[3])) -
+                         slice_sum<MM>(cc[fn]);
+      // Opaque copy of tau for the screen only.  Measured, not reasoned:
+      // without it the K-panel loop of the huge no-injection kernel is
+      // scheduled slightly differently and runs 0.6% slower; with it the
+      // loop is nearly the unscreened kernel's (docs/ABLATION.md §5a).
+      float tau_o = tau;
+      asm volatile("" : "+v"(tau_o));
+      if (!__any(fabsf(rc32) > 0.5f * tau_o)) continue;
+    }
+
+    // fp64 PLAIN column sum: the fault itself (|e| ~ 1e4) sits in this
+    // sum, so an fp32 accumulation rounds every later term at ulp(1e4)
+    // ~ 1e-3 and the CORRECTION (rc is subtracted from the output)
+    // inherits ~5e-3..1e-2 of error (found by tools/soak.py at
+    // |alpha| > 1).  The WEIGHTED sum stays fp32: rw only selects an
+    // integer row via round(rw/rc), its baseline cw is fp32-maintained
+    // anyway, and the fp32 noise is ~1e-4 of a row index — while the
+    // fp64 weight conversions were what spilled ~143 dwords/lane in the
+    // stream-K fused variants (cold-path scratch traffic ~1 GB/GEMM).
+    //
+    // Opaque copy of `sub`: everything derived from it (the FM*NREG
+    // per-lane row weights below) is materialised INSIDE this cold block.
+    // Without it the compiler hoists the loop-invariant weights into the
+    // kernel prologue and keeps them live through the whole hot loop
+    // (+68 VGPRs measured on the 64x64-wave tile -> spills on the bigger
+    // tiles).
+    int sub_o = sub;  // fresh opaque copy per fn: stops the
+    asm volatile("" : "+v"(sub_o));  // weights being CSE'd+spilled
+    double colp = 0.0;
+    float colwf = 0.f;
+#pragma unroll
+    for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+      for (int reg = 0; reg < NREG; ++reg) {
+        const float v = acc[fm][fn][reg];
+        colp += (double)v;
+        colwf = fmaf((float)(fm * MM + acc_row(reg, sub_o)), v, colwf);
+      }
+    const float rc =
+        (float)(dslice_sum<MM>(colp) - (double)slice_sum<MM>(cc[fn]));
+    const float rw = slice_sum<MM>(colwf) - slice_sum<MM>(cw[fn]);
+    const bool cbad = fabsf(rc) > tau;
+    const int row = (int)rintf(rw / (cbad ? rc : 1.f));
+    int sub_c = sub;  // independent opaque copy for the correct pass
+    asm volatile("" : "+v"(sub_c));
+#pragma unroll
+    for (int fm = 0; fm < FM; ++fm) {
+      // a blended row outside [0, FM*MM) matches no fm: the fail-safe
+      if (FM > 1 && !__any(cbad && row >= fm * MM && row < (fm + 1) * MM))
+        continue;
+#pragma unroll
+      for (int reg = 0; reg < NREG; ++reg) {
+        const bool hit = cbad && (fm * MM + acc_row(reg, sub_c) == row);
+        acc[fm][fn][reg] -= hit ? rc : 0.f;
+      }
+    }
+  }
+}
+
 // Segment-sum precompute: for a column-major MxK matrix, per SEG-row band,
 // the plain column sum s = sum_{i in [seg*SEG, +SEG)} A[i + k*M] and the
 // row-index-weighted sum w = sum_i (i % SEG) * A[i + k*M] used by the
@@ -293,8 +388,9 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
 
   // ---- ABFT verify / locate / correct: wave-autonomous, registers only ----
   // Two-phase: a cheap detect (compare the total tile sum against the total
-  // checksum — FM*FN*NREG adds + a butterfly) runs every verify window; the locate/correct
-  // below is entered only when the residual trips the threshold (i.e. in
+  // checksum — FM*FN*NREG adds + a butterfly) runs every verify window;
+  // locate_correct() (above, shared with the stream-K kernel) is entered
+  // only when the residual trips the threshold (i.e. in
   // the wave that actually absorbed a fault), so the fault-free common case
   // never pays for location.
   //
@@ -317,58 +413,11 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
   // fragment's row range nothing matches and the kernel fail-safes to
   // detected-but-uncorrected.  Faults in different columns (the common
   // double-fault shape) locate independently per lane and correct fine.
-  auto locate_correct = [&]() __attribute__((always_inline)) {
-    // Opaque copy of `sub`: everything derived from it (the 2*FM*NREG
-    // per-lane row weights below) is materialised INSIDE this cold block.
-    // Without it the compiler hoists the loop-invariant weights into the
-    // kernel prologue and keeps them live through the whole hot loop
-    // (+68 VGPRs measured on the 64x64-wave tile -> spills on the bigger
-    // tiles).
-#pragma unroll
-    for (int fn = 0; fn < FN; ++fn) {
-      // fp64 PLAIN column sum: the fault itself (|e| ~ 1e4) sits in this
-      // sum, so an fp32 accumulation rounds every later term at ulp(1e4)
-      // ~ 1e-3 and the CORRECTION (rc is subtracted from the output)
-      // inherits ~5e-3..1e-2 of error (found by tools/soak.py at
-      // |alpha| > 1).  The WEIGHTED sum stays fp32: rw only selects an
-      // integer row via round(rw/rc), its baseline cw is fp32-maintained
-      // anyway, and the fp32 noise is ~1e-4 of a row index — while the
-      // fp64 weight conversions were what spilled ~143 dwords/lane in the
-      // stream-K fused variants (cold-path scratch traffic ~1 GB/GEMM).
-      int sub_o = sub;  // fresh opaque copy per fn: stops the
-      asm volatile("" : "+v"(sub_o));  // weights being CSE'd+spilled
-      double colp = 0.0;
-      float colwf = 0.f;
-#pragma unroll
-      for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-        for (int reg = 0; reg < NREG; ++reg) {
-          const float v = acc[fm][fn][reg];
-          colp += (double)v;
-          colwf = fmaf((float)(fm * MM + acc_row(reg, sub_o)), v, colwf);
-        }
-      const float rc =
-          (float)(dslice_sum<MM>(colp) - (double)slice_sum<MM>(cc[fn]));
-      const float rw = slice_sum<MM>(colwf) - slice_sum<MM>(cw[fn]);
-      const bool cbad = fabsf(rc) > tau;
-      const int row = (int)rintf(rw / (cbad ? rc : 1.f));
-      int sub_c = sub;  // independent opaque copy for the correct pass
-      asm volatile("" : "+v"(sub_c));
-#pragma unroll
-      for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-        for (int reg = 0; reg < NREG; ++reg) {
-          const bool hit = cbad && (fm * MM + acc_row(reg, sub_c) == row);
-          acc[fm][fn][reg] -= hit ? rc : 0.f;
-        }
-    }
-  };
-
   auto verify_correct = [&]() __attribute__((always_inline)) {
     // Cheap detect: total tile sum vs total checksum (FM*FN*NREG adds + 6
     // shuffles).  The residual is identical across the wave's lanes, so
     // the branch is uniform; only a wave that actually absorbed a fault
-    // enters the locate/correct path above.
+    // enters locate_correct().
     float tot = 0.f, chk = 0.f;
 #pragma unroll
     for (int fn = 0; fn < FN; ++fn) {
@@ -381,7 +430,8 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
     float res = tot - chk;
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) res += __shfl_xor(res, m, 64);
-    if (__builtin_expect(fabsf(res) > tau, 0)) locate_correct();
+    if (__builtin_expect(fabsf(res) > tau, 0))
+      locate_correct<FM, FN, MM>(acc, cc, cw, sub, tau);
   };
 
   // ---- main K loop: one barrier per BK panel, glds prefetch overlaps ----

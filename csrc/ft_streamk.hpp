@@ -233,42 +233,9 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
 #pragma unroll
   for (int fn = 0; fn < FN; ++fn) cc[fn] = cw[fn] = 0.f;
 
-    // verify/locate/correct: identical maths to the classic kernel
-    // (csrc/ft_kernels.hpp locate_correct/verify_correct), operating on
+    // verify + the shared locate_correct() of csrc/ft_kernels.hpp: the
+    // same detect as the classic kernel's verify_correct, operating on
     // this workgroup's PARTIAL k-range accumulation.
-    auto locate_correct = [&]() __attribute__((always_inline)) {
-#pragma unroll
-      for (int fn = 0; fn < FN; ++fn) {
-        // fp64 plain sum (correction magnitude), fp32 weighted sum (row
-        // index only) — see the classic kernel's locate_correct note.
-        int sub_o = sub;  // fresh opaque copy per fn (see classic)
-        asm volatile("" : "+v"(sub_o));
-        double colp = 0.0;
-        float colwf = 0.f;
-#pragma unroll
-        for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-          for (int reg = 0; reg < NREG; ++reg) {
-            const float v = acc[fm][fn][reg];
-            colp += (double)v;
-            colwf = fmaf((float)(fm * MM + acc_row(reg, sub_o)), v, colwf);
-          }
-        const float rc =
-            (float)(dslice_sum<MM>(colp) - (double)slice_sum<MM>(cc[fn]));
-        const float rw = slice_sum<MM>(colwf) - slice_sum<MM>(cw[fn]);
-        const bool cbad = fabsf(rc) > tau;
-        const int row = (int)rintf(rw / (cbad ? rc : 1.f));
-        int sub_c = sub;  // independent opaque copy for the correct pass
-        asm volatile("" : "+v"(sub_c));
-#pragma unroll
-        for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-          for (int reg = 0; reg < NREG; ++reg) {
-            const bool hit = cbad && (fm * MM + acc_row(reg, sub_c) == row);
-            acc[fm][fn][reg] -= hit ? rc : 0.f;
-          }
-      }
-    };
     auto verify_correct = [&]() __attribute__((always_inline)) {
       float tot = 0.f, chk = 0.f;
 #pragma unroll
@@ -282,7 +249,8 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
       float res = tot - chk;
 #pragma unroll
       for (int m = 1; m < 64; m <<= 1) res += __shfl_xor(res, m, 64);
-      if (__builtin_expect(fabsf(res) > tau, 0)) locate_correct();
+      if (__builtin_expect(fabsf(res) > tau, 0))
+        locate_correct<FM, FN, MM>(acc, cc, cw, sub, tau);
     };
 
   while (u < u_end) {

@@ -103,6 +103,35 @@ bool tier_supported(int64_t tier, int64_t M, int64_t N, int64_t K) {
   return ftsgemm::sgemm_tier_supported((int)tier, (int)M, (int)N, (int)K);
 }
 
+// idesc: (ncases, 9) int32, fdesc: (ncases, 3) fp32 — see ft_core.h.
+// Returns the (3, ncases, fm*fn*nreg, 64) {shipped, reference, clean} tiles.
+at::Tensor locate_selftest(int64_t fm, int64_t fn, int64_t mm,
+                           at::Tensor idesc, at::Tensor fdesc, double amp) {
+  TORCH_CHECK(idesc.is_cuda() && fdesc.is_cuda(),
+              "locate_selftest: descriptors must be on a GPU device");
+  TORCH_CHECK(idesc.scalar_type() == at::kInt && idesc.is_contiguous() &&
+                  idesc.dim() == 2 && idesc.size(1) == 9,
+              "locate_selftest: idesc must be contiguous int32 (ncases, 9)");
+  const int64_t ncases = idesc.size(0);
+  TORCH_CHECK(fdesc.scalar_type() == at::kFloat && fdesc.is_contiguous() &&
+                  fdesc.dim() == 2 && fdesc.size(0) == ncases &&
+                  fdesc.size(1) == 3,
+              "locate_selftest: fdesc must be contiguous fp32 (ncases, 3)");
+  TORCH_CHECK(ncases >= 1 && ncases <= (1 << 20),
+              "locate_selftest: 1..2^20 cases");
+  const int64_t nreg = mm == 32 ? 16 : 4;
+  at::Tensor out = at::empty({3, ncases, fm * fn * nreg, 64},
+                             fdesc.options());
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipError_t err = ftsgemm::locate_selftest_launch(
+      (int)fm, (int)fn, (int)mm, (int)ncases, idesc.const_data_ptr<int>(),
+      fdesc.const_data_ptr<float>(), (float)amp,
+      out.mutable_data_ptr<float>(), stream.stream());
+  TORCH_CHECK(err == hipSuccess, "locate_selftest: unsupported (fm, fn, mm) ",
+              "or launch failure: ", hipGetErrorString(err));
+  return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -110,4 +139,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rocblas_sgemm", &rocblas_sgemm_nt, "rocBLAS oracle SGEMM");
   m.def("baseline_ft", &baseline_ft, "non-fused rocBLAS ABFT baseline");
   m.def("tier_supported", &tier_supported, "tile divisibility check");
+  m.def("locate_selftest", &locate_selftest,
+        "device self-test of the ABFT locate/correct");
 }

@@ -72,6 +72,18 @@ def baseline_ft(a, b, c, alpha: float = 1.0, beta: float = 0.0,
     return c, res
 
 
+def locate_selftest(fm: int, fn: int, mm: int, idesc: torch.Tensor,
+                    fdesc: torch.Tensor, amp: float) -> torch.Tensor:
+    """Device self-test of the fused kernels' locate/correct on a synthetic
+    fm x fn wave tile of mm-wide MFMA fragments, one single-wave block per
+    case.  idesc (ncases, 9) int32 = {nfault, (fm, fn, reg, lane) x 2},
+    fdesc (ncases, 3) fp32 = {mag0, mag1, tau}; clean accumulators are a
+    hash in (-amp, amp).  Returns (3, ncases, fm*fn*nreg, 64): the tile
+    corrected by the shipped function, by the sweep-everything reference
+    form, and the clean tile."""
+    return _require_ext().locate_selftest(fm, fn, mm, idesc, fdesc, amp)
+
+
 def choose_tier(m: int, n: int, k: int):
     """Pick the fastest applicable tier for a problem shape, or None when no
     hand-tiled tier divides the shape (callers fall back to rocBLAS).

@@ -36,7 +36,9 @@ def init_from_env(backend: Optional[str] = None) -> tuple[int, int]:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29571")
         dist.init_process_group(backend=backend, rank=rank, world_size=world)
-        if torch.cuda.is_available():
+        # one GPU per rank on the device backend only: a gloo (CPU) job may
+        # run more ranks than the box has GPUs
+        if backend == "nccl" and torch.cuda.is_available():
             torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", rank)))
     return rank, world
 

@@ -28,6 +28,7 @@ setup(
                 "csrc/torch_ext.cpp",
                 "csrc/dispatch.hip",
                 "csrc/rocblas_path.hip",
+                "csrc/locate_selftest.hip",
             ] + sorted(p for p in glob.glob("csrc/generated/kernel_*.hip")
                        if not p.endswith("_hip.hip")),
             include_dirs=[os.path.join(ROOT, "csrc")],
