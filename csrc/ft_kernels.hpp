@@ -115,6 +115,57 @@ __device__ constexpr int acc_row(int reg, int sub) {
   return (reg & 3) + 8 * (reg >> 2) + 4 * sub;
 }
 
+// One lane's running column checksums of its wave tile: per fragment column
+// fn the plain checksum cc (col r of frag fn, this lane's k-slices only) and
+// the row-index-weighted one cw (ratio locate: fault row =
+// round(residual(cw) / residual(cc))).  They live in register PAIRS laid
+// out so that each encode step is a whole v_pk_fma_f32 whose broadcast
+// operand is a half the instruction can select by itself (op_sel), with no
+// v_mov to build it (docs/ABLATION.md §5b):
+//   FN even: v[2j] = (cc[2j], cc[2j+1]), v[2j+1] = (cw[2j], cw[2j+1]) —
+//            the B pair is used as loaded, the segment sum is broadcast;
+//   FN odd:  v[fn] = (cc[fn], cw[fn]) — the segment-sum pair is used as
+//            loaded, the B value is broadcast.
+// Every component is one fused multiply-add per k-slice, in ascending k:
+// the same bits as the scalar fmaf chain.
+template <int FN> struct checksum_regs {
+  static constexpr bool PAIRED = FN % 2 == 0;
+  f32x2 v[FN];
+  __device__ inline void clear() {
+#pragma unroll
+    for (int i = 0; i < FN; ++i) v[i] = f32x2{0.f, 0.f};
+  }
+  // sw = (plain, row-weighted) segment sum of this lane's k-slice
+  __device__ inline void encode(f32x2 sw, const float (&b)[FN]) {
+    if constexpr (PAIRED) {
+#pragma unroll
+      for (int j = 0; j < FN / 2; ++j) {
+        const f32x2 bp{b[2 * j], b[2 * j + 1]};
+        v[2 * j] = __builtin_elementwise_fma(f32x2{sw[0], sw[0]}, bp, v[2 * j]);
+        v[2 * j + 1] =
+            __builtin_elementwise_fma(f32x2{sw[1], sw[1]}, bp, v[2 * j + 1]);
+      }
+    } else {
+#pragma unroll
+      for (int fn = 0; fn < FN; ++fn)
+        v[fn] = __builtin_elementwise_fma(sw, f32x2{b[fn], b[fn]}, v[fn]);
+    }
+  }
+  __device__ inline float cc(int fn) const {
+    return PAIRED ? v[fn & ~1][fn & 1] : v[fn][0];
+  }
+  __device__ inline float cw(int fn) const {
+    return PAIRED ? v[fn | 1][fn & 1] : v[fn][1];
+  }
+};
+
+// Whether the fused panel loop parks its strip reads and runs the encode
+// behind the panel barrier (see the panel loop of sgemm_mfma).  The
+// single-fragment tiers (medium, small: one MFMA per k-step) keep the encode
+// next to its read: deferring removes no LGKM drain from their loop, and
+// costs the small tier 10 VGPRs and with them a wave of occupancy.
+template <int FM, int FN> constexpr bool defer_encode = FM * FN > 1;
+
 // ABFT ratio locate + in-register correct of one wave tile, shared by the
 // classic and the stream-K kernel (entered only after the cheap detect in
 // their verify_correct tripped; the scheme itself is described there).
@@ -288,10 +339,8 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
   const int jn0 = by * BN;
 
   typename T::acc_t acc[FM][FN] = {};
-  float cc[FN] = {};  // running column checksum of this wave's tile (per
-                      // lane: col r of frag fn, this lane's k-slices only)
-  float cw[FN] = {};  // row-index-weighted column checksum (ratio locate:
-                      // fault row = round(residual(cw) / residual(cc)))
+  checksum_regs<FN> cs;  // running column checksums of this wave's tile
+  cs.clear();
 
   // ---- async HBM -> LDS staging (global_load_lds, 16 B per lane) ----
   // staging passes may be fractional in WHOLE WAVES (e.g. the fused tall
@@ -419,8 +468,11 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
     // the branch is uniform; only a wave that actually absorbed a fault
     // enters locate_correct().
     float tot = 0.f, chk = 0.f;
+    float cc[FN], cw[FN];
 #pragma unroll
     for (int fn = 0; fn < FN; ++fn) {
+      cc[fn] = cs.cc(fn);
+      cw[fn] = cs.cw(fn);
       chk += cc[fn];
 #pragma unroll
       for (int fm = 0; fm < FM; ++fm)
@@ -478,8 +530,27 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
           ABFT ? &lds[STRIP_OFF + wave * 256 + ((it / PPS) & 1) * 128 +
                       (it % PPS) * BK * 2]
                : nullptr;
+      // Encode (reference encode: ft_sgemm_huge.cuh:150-213, redesigned
+      // around the offline segsum pass + ratio locate): per k-slice ONE
+      // ds_read_b64 fetches the interleaved (plain, row-weighted)
+      // segment-sum pair, and cs.encode() adds its two fmas per B fragment.
+      // Where a k-step has more than one MFMA (defer_encode) the fused loop
+      // keeps the plain loop's LDS wait structure: the strip reads only
+      // PARK their pair next to the B fragments (which stay in registers
+      // until the panel's last MFMA anyway) and the encode runs as one
+      // block BEHIND the panel barrier, in the shadow of the MFMAs the
+      // compiler sinks there.  With the fmas next to the reads, LDS
+      // returning in order forced a full lgkmcnt(0) drain per k-step.  A
+      // source reorder alone is undone by the scheduler; the empty asm on
+      // the pairs, ordered after the barrier, is what pins it
+      // (docs/ABLATION.md §5b).  Per lane the fmas into each checksum
+      // still run in ascending k: bit-identical.
+      constexpr int NKK = BK / KSTEP;
+      constexpr bool DEFER = ABFT && defer_encode<FM, FN>;
+      f32x2 swv[DEFER ? NKK : 1];
+      float bv[DEFER ? NKK : 1][FN];
 #pragma unroll
-      for (int kk = 0; kk < BK / KSTEP; ++kk) {
+      for (int kk = 0; kk < NKK; ++kk) {
         const int kloc = kk * KSTEP + sub;
         float a[FM], b[FN];
 #pragma unroll
@@ -489,18 +560,12 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
         for (int fn = 0; fn < FN; ++fn)
           b[fn] = Bs[kloc * BN + wj0 + fn * MM + r];
 
-        if constexpr (ABFT) {
-          // Encode: ONE ds_read_b64 fetches the interleaved (plain,
-          // row-weighted) segment-sum pair for this k-slice + two fmas
-          // per B fragment into the running column checksums (reference
-          // encode: ft_sgemm_huge.cuh:150-213, redesigned around the
-          // offline segsum pass + ratio locate).
-          const f32x2 sw = *(const f32x2*)(strip + 2 * kloc);
+        if constexpr (DEFER) {
+          swv[kk] = *(const f32x2*)(strip + 2 * kloc);
 #pragma unroll
-          for (int fn = 0; fn < FN; ++fn) {
-            cc[fn] = fmaf(sw[0], b[fn], cc[fn]);
-            cw[fn] = fmaf(sw[1], b[fn], cw[fn]);
-          }
+          for (int fn = 0; fn < FN; ++fn) bv[kk][fn] = b[fn];
+        } else if constexpr (ABFT) {
+          cs.encode(*(const f32x2*)(strip + 2 * kloc), b);
         }
 
         // interleave VMEM/DS/MFMA scheduling groups (+1% measured)
@@ -512,6 +577,12 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
             acc[fm][fn] = T::mma(a[fm], b[fn], acc[fm][fn]);
       }
       __syncthreads();
+      if constexpr (DEFER) {
+#pragma unroll
+        for (int kk = 0; kk < NKK; ++kk) asm volatile("" : "+v"(swv[kk]));
+#pragma unroll
+        for (int kk = 0; kk < NKK; ++kk) cs.encode(swv[kk], bv[kk]);
+      }
     }
     if constexpr (ABFT) verify_correct();
   }

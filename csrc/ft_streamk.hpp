@@ -224,22 +224,23 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
   // loop body made the allocator keep per-iteration copies alive and spill
   // 142 VGPRs in the fused variants (measured; the plain variant fit).
   typename T::acc_t acc[FM][FN];
-  float cc[FN];
-  float cw[FN];
+  checksum_regs<FN> cs;
 #pragma unroll
   for (int fm = 0; fm < FM; ++fm)
 #pragma unroll
     for (int fn = 0; fn < FN; ++fn) acc[fm][fn] = {};
-#pragma unroll
-  for (int fn = 0; fn < FN; ++fn) cc[fn] = cw[fn] = 0.f;
+  cs.clear();
 
     // verify + the shared locate_correct() of csrc/ft_kernels.hpp: the
     // same detect as the classic kernel's verify_correct, operating on
     // this workgroup's PARTIAL k-range accumulation.
     auto verify_correct = [&]() __attribute__((always_inline)) {
       float tot = 0.f, chk = 0.f;
+      float cc[FN], cw[FN];
 #pragma unroll
       for (int fn = 0; fn < FN; ++fn) {
+        cc[fn] = cs.cc(fn);
+        cw[fn] = cs.cw(fn);
         chk += cc[fn];
 #pragma unroll
         for (int fm = 0; fm < FM; ++fm)
@@ -297,8 +298,14 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
             ABFT ? &lds[STRIP_OFF + wave * 256 + ((w_lo + p / PPS) & 1) * 128 +
                         (p % PPS) * BK * 2]
                  : nullptr;
+        // strip reads parked, encode behind the barrier: see the classic
+        // kernel's panel loop (ft_kernels.hpp)
+        constexpr int NKK = BK / KSTEP;
+        constexpr bool DEFER = ABFT && defer_encode<FM, FN>;
+        f32x2 swv[DEFER ? NKK : 1];
+        float bv[DEFER ? NKK : 1][FN];
 #pragma unroll
-        for (int kk = 0; kk < BK / KSTEP; ++kk) {
+        for (int kk = 0; kk < NKK; ++kk) {
           const int kloc = kk * KSTEP + sub;
           float a[FM], b[FN];
 #pragma unroll
@@ -307,13 +314,12 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
 #pragma unroll
           for (int fn = 0; fn < FN; ++fn)
             b[fn] = Bs[kloc * BN + wj0 + fn * MM + r];
-          if constexpr (ABFT) {
-            const f32x2 sw = *(const f32x2*)(strip + 2 * kloc);
+          if constexpr (DEFER) {
+            swv[kk] = *(const f32x2*)(strip + 2 * kloc);
 #pragma unroll
-            for (int fn = 0; fn < FN; ++fn) {
-              cc[fn] = fmaf(sw[0], b[fn], cc[fn]);
-              cw[fn] = fmaf(sw[1], b[fn], cw[fn]);
-            }
+            for (int fn = 0; fn < FN; ++fn) bv[kk][fn] = b[fn];
+          } else if constexpr (ABFT) {
+            cs.encode(*(const f32x2*)(strip + 2 * kloc), b);
           }
           __builtin_amdgcn_iglp_opt(0);
 #pragma unroll
@@ -323,6 +329,12 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
               acc[fm][fn] = T::mma(a[fm], b[fn], acc[fm][fn]);
         }
         __syncthreads();
+        if constexpr (DEFER) {
+#pragma unroll
+          for (int kk = 0; kk < NKK; ++kk) asm volatile("" : "+v"(swv[kk]));
+#pragma unroll
+          for (int kk = 0; kk < NKK; ++kk) cs.encode(swv[kk], bv[kk]);
+        }
       }
       if constexpr (ABFT) verify_correct();
     }
@@ -388,10 +400,7 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
       for (int fm = 0; fm < FM; ++fm)
 #pragma unroll
         for (int fn = 0; fn < FN; ++fn) acc[fm][fn] = {};
-      if constexpr (ABFT) {
-#pragma unroll
-        for (int fn = 0; fn < FN; ++fn) cc[fn] = cw[fn] = 0.f;
-      }
+      if constexpr (ABFT) cs.clear();
     }
   }
 }
