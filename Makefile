@@ -13,7 +13,7 @@ cli: bin/ft_sgemm
 # filter out PyTorch-hipify byproducts (kernel_*_hip.hip copies)
 KERNEL_TUS := $(filter-out %_hip.hip, $(wildcard csrc/generated/kernel_*.hip))
 
-bin/ft_sgemm: csrc/cli_main.hip csrc/dispatch.hip csrc/rocblas_path.hip csrc/locate_selftest.hip csrc/ft_kernels.hpp csrc/ft_streamk.hpp csrc/tier_launch.hpp csrc/ft_core.h csrc/generated/tile_params.h $(KERNEL_TUS)
+bin/ft_sgemm: csrc/cli_main.hip csrc/dispatch.hip csrc/rocblas_path.hip csrc/locate_selftest.hip csrc/ft_kernels.hpp csrc/ft_streamk.hpp csrc/tier_launch.hpp csrc/ft_core.h csrc/fault_log.h csrc/generated/tile_params.h $(KERNEL_TUS)
 	mkdir -p bin
 	$(HIPCC) -x hip --offload-arch=$(ARCH) -O3 -std=c++17 -Icsrc $(FTFLAGS) \
 	  csrc/cli_main.hip csrc/dispatch.hip csrc/rocblas_path.hip \

@@ -12,7 +12,8 @@
 // The FT kernels (ids 11-16) run with the always-on fault injector, so a
 // passing verification proves in-kernel detect+locate+correct end to end
 // (SURVEY.md section 4 item 2).  Set FT_SGEMM_NO_INJECT=1 to measure the
-// ABFT overhead without injection.
+// ABFT overhead without injection.  Set FT_SGEMM_REPORT=1 to attach a fault
+// log to every fused id in the verification pass and print its counters.
 
 #include <hip/hip_runtime.h>
 
@@ -62,7 +63,8 @@ float* abft_ws(size_t floats) {
 
 bool run_kernel(int kid, int M, int N, int K, const float* dA,
                 const float* dB, float* dC, float alpha, float beta,
-                const ftsgemm::BaselineWorkspace& ws, bool inject) {
+                const ftsgemm::BaselineWorkspace& ws, bool inject,
+                const ftsgemm::FaultLog* log = nullptr) {
   if (kid >= 1 && kid <= 6)
     return ftsgemm::sgemm_tier_launch(kid - 1, false, false, M, N, K, dA, dB,
                                       dC, alpha, beta, kTau, kInj, 20,
@@ -72,7 +74,7 @@ bool run_kernel(int kid, int M, int N, int K, const float* dA,
         ftsgemm::sgemm_abft_workspace_floats(kid - 11, M, N, K));
     return ftsgemm::sgemm_tier_launch(kid - 11, true, inject, M, N, K, dA,
                                       dB, dC, alpha, beta, kTau, kInj, 20,
-                                      w, 0) == hipSuccess;
+                                      w, 0, log) == hipSuccess;
   }
   if (kid == 10) {
     // panel width sized for MI355X (the reference's 256 is T4-sized: at
@@ -108,6 +110,17 @@ int main(int argc, char** argv) {
   const char* json_env = getenv("FT_SGEMM_JSON");  // machine-readable lines
   FILE* jf = nullptr;
   if (json_env && *json_env) jf = fopen(json_env, "w");
+  // FT_SGEMM_REPORT: fault log for the fused ids of the verification pass
+  const char* rep_env = getenv("FT_SGEMM_REPORT");
+  const bool report = rep_env && *rep_env && strcmp(rep_env, "0") != 0;
+  ftsgemm::FaultLog flog;
+  if (report) {
+    flog.capacity = 1024;
+    HIP_CALL(hipMalloc(&flog.counters, ftsgemm::FLOG_N_COUNTERS * sizeof(int)));
+    HIP_CALL(hipMalloc(&flog.events, (size_t)flog.capacity *
+                                         ftsgemm::FLOG_EVENT_DWORDS *
+                                         sizeof(int)));
+  }
   const int reps = 5;
   const float alpha = 1.f;
   // END < START runs the verification pass only (tools/race_check.sh);
@@ -157,11 +170,17 @@ int main(int argc, char** argv) {
   // ---------------- verification pass ----------------
   const int vM = start, vN = start, vK = start;
   std::vector<float> hC(maxn * maxn), hCref(maxn * maxn);
+  char fault_json[17][128] = {};  // per id: the verify pass's fault counts
   printf("verify at M=N=K=%d\n", vM);
   for (int kid = k0; kid <= k1 && kid <= 16; ++kid) {
     ftsgemm::rocblas_sgemm_nt(vM, vN, vK, dA, dB, dCref, 1.f, 0.f, 0);
     HIP_CALL(hipMemset(dC, 0, (size_t)vM * vN * sizeof(float)));
-    if (!run_kernel(kid, vM, vN, vK, dA, dB, dC, 1.f, 0.f, ws, inject)) {
+    const bool logged = report && kid >= 11 && kid <= 16;
+    if (logged)
+      HIP_CALL(hipMemset(flog.counters, 0,
+                         ftsgemm::FLOG_N_COUNTERS * sizeof(int)));
+    if (!run_kernel(kid, vM, vN, vK, dA, dB, dC, 1.f, 0.f, ws, inject,
+                    logged ? &flog : nullptr)) {
       printf("kernel %2d %-20s LAUNCH FAILED\n", kid, kNames[kid]);
       continue;
     }
@@ -193,6 +212,20 @@ int main(int argc, char** argv) {
       }
     }
     if (ok) printf("kernel %2d %-20s verified\n", kid, kNames[kid]);
+    if (logged) {
+      int cnt[ftsgemm::FLOG_N_COUNTERS];
+      HIP_CALL(hipMemcpy(cnt, flog.counters, sizeof cnt,
+                         hipMemcpyDeviceToHost));
+      printf("faults: tripped %d corrected %d uncorrected %d unlocated %d\n",
+             cnt[ftsgemm::FLOG_TRIPPED], cnt[ftsgemm::FLOG_CORRECTED],
+             cnt[ftsgemm::FLOG_UNCORRECTED], cnt[ftsgemm::FLOG_UNLOCATED]);
+      // kept for this id's JSON lines (written by the sweep below)
+      snprintf(fault_json[kid], sizeof fault_json[kid],
+               ", \"tripped\": %d, \"corrected\": %d, \"uncorrected\": %d, "
+               "\"unlocated\": %d",
+               cnt[ftsgemm::FLOG_TRIPPED], cnt[ftsgemm::FLOG_CORRECTED],
+               cnt[ftsgemm::FLOG_UNCORRECTED], cnt[ftsgemm::FLOG_UNLOCATED]);
+    }
   }
 
   // ---------------- perf sweep ----------------
@@ -242,9 +275,9 @@ int main(int argc, char** argv) {
       if (jf)
         fprintf(jf,
                 "{\"kernel_id\": %d, \"name\": \"%s\", \"n\": %d, "
-                "\"gflops\": %.1f, \"reps\": %d, \"inject\": %s}\n",
+                "\"gflops\": %.1f, \"reps\": %d, \"inject\": %s%s}\n",
                 kid, kNames[kid], n, gflops, reps,
-                (kid >= 11 && inject) ? "true" : "false");
+                (kid >= 11 && inject) ? "true" : "false", fault_json[kid]);
       HIP_CALL(hipEventDestroy(beg));
       HIP_CALL(hipEventDestroy(fin));
       fflush(stdout);

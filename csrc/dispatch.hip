@@ -16,7 +16,7 @@ namespace ftsgemm {
                                 const float* A, const float* B, float* C,    \
                                 float alpha, float beta, float tau,          \
                                 float inj_mag, int verify_windows, float* ws,\
-                                hipStream_t stream);                         \
+                                hipStream_t stream, const FaultLog* log);    \
   size_t abft_ws_floats_##name(int M, int N, int K);
 FT_TIER_LIST(FT_DECL)
 #undef FT_DECL
@@ -25,12 +25,13 @@ hipError_t sgemm_tier_launch(int tier, bool abft, bool inject, int M, int N,
                              int K, const float* A, const float* B, float* C,
                              float alpha, float beta, float tau,
                              float inj_mag, int verify_windows, float* ws,
-                             hipStream_t stream) {
+                             hipStream_t stream, const FaultLog* log) {
   switch (tier) {
 #define FT_CASE(name, BM, BN, BK, WM, WN, MM)                              \
   case FT_TIER_ID_##name:                                                  \
     return launch_tier_##name(abft, inject, M, N, K, A, B, C, alpha, beta, \
-                              tau, inj_mag, verify_windows, ws, stream);
+                              tau, inj_mag, verify_windows, ws, stream,    \
+                              log);
     FT_TIER_LIST(FT_CASE)
 #undef FT_CASE
     default:

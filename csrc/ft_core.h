@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "fault_log.h"
+
 namespace ftsgemm {
 
 // Launch one of the six hand-tiled MFMA SGEMM kernels (tier id per
@@ -12,11 +14,17 @@ namespace ftsgemm {
 // When abft, `ws` must point to a device scratch buffer of
 // sgemm_abft_workspace_floats(tier, M, N, K) fp32 elements (the launcher
 // fills it with the segment checksums of A and B before the fused kernel).
+// `log` (optional, fused variants only) attaches a caller-owned fault log
+// (fault_log.h): the kernels' locate/correct path adds to its counters and
+// appends one event per detected fault.  The launch neither zeroes,
+// allocates nor syncs for it — counts accumulate until the caller clears
+// them — and with log == nullptr the kernels write nothing.
 hipError_t sgemm_tier_launch(int tier, bool abft, bool inject, int M, int N,
                              int K, const float* A, const float* B, float* C,
                              float alpha, float beta, float tau,
                              float inj_mag, int verify_windows, float* ws,
-                             hipStream_t stream);
+                             hipStream_t stream,
+                             const FaultLog* log = nullptr);
 
 bool sgemm_tier_supported(int tier, int M, int N, int K);
 
@@ -33,6 +41,18 @@ size_t sgemm_abft_workspace_floats(int tier, int M, int N, int K);
 hipError_t locate_selftest_launch(int fm, int fn, int mm, int ncases,
                                   const int* idesc, const float* fdesc,
                                   float amp, float* out, hipStream_t stream);
+
+// Report variant of the self-test: runs only the shipped locate_correct, in
+// its fault-log form, on the same descriptors.  Every case has a log of its
+// own: counters is [ncases][FLOG_N_COUNTERS] and events
+// [ncases][capacity][FLOG_EVENT_DWORDS] int32, both zeroed by the caller;
+// the wave tile sits at origin (0, 0) with k range [0, 0).
+// out: [ncases][FM*FN*NREG][64] floats, the corrected tile.
+hipError_t locate_selftest_report_launch(int fm, int fn, int mm, int ncases,
+                                         const int* idesc, const float* fdesc,
+                                         float amp, float* out, int* counters,
+                                         int* events, int capacity,
+                                         hipStream_t stream);
 
 // rocBLAS paths (kernel id 0 oracle and the id-10 non-fused ABFT baseline,
 // reference: cuBLAS at sgemm.cu:108 / include/baseline_ft_sgemm.cuh).

@@ -41,6 +41,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "fault_log.h"
+
 // FT_PARANOID (race-check build, `make cli-paranoid`): drain ALL
 // outstanding async staging (glds vmcnt + LDS lgkm) and barrier right at
 // every staging site.  Per-thread arithmetic order is unchanged, so the
@@ -166,6 +168,15 @@ template <int FN> struct checksum_regs {
 // costs the small tier 10 VGPRs and with them a wave of occupancy.
 template <int FM, int FN> constexpr bool defer_encode = FM * FN > 1;
 
+// What locate_correct needs to report a fault: the log and where the wave
+// tile sits.  (i0, j0) is the wave tile's first global row / column,
+// [k_begin, k_end) the verify window (classic) or work-unit group
+// (stream-K) whose accumulation is being checked.
+struct FaultCtx {
+  FaultLog log;
+  int i0 = 0, j0 = 0, k_begin = 0, k_end = 0;
+};
+
 // ABFT ratio locate + in-register correct of one wave tile, shared by the
 // classic and the stream-K kernel (entered only after the cheap detect in
 // their verify_correct tripped; the scheme itself is described there).
@@ -183,11 +194,30 @@ template <int FM, int FN> constexpr bool defer_encode = FM * FN > 1;
 //     located its row in.
 // The arithmetic on a column that IS processed is the unscreened one, in
 // the same order, so outputs are bit-identical to sweeping everything.
-template <int FM, int FN, int MM>
+//
+// This is also the ONE place that writes the fault log (fault_log.h), for
+// both callers, in the LOG instantiation only: a null-pointer test in one
+// shared instantiation cost every fused kernel 2-5 VGPRs and the tall tier
+// a wave of occupancy (docs/ABLATION.md §5c), so the launchers pick the LOG
+// twin when a log is attached and the kernels that run without one are the
+// unlogged code.  ctx is built by the caller inside its tripped branch.
+// Per entry: tripped += 1; per bad column one event, counted
+// as corrected when the located row is inside the wave tile and as
+// uncorrected (the fail-safe) otherwise; unlocated += 1 when no column was
+// bad.  After the slice sums rc and row are identical in the 64/MM lanes
+// that share a column, so the lane with sub == 0 reports for all of them.
+// The log only reads what the locate computed: acc is corrected exactly as
+// without it.
+template <int FM, int FN, int MM, bool LOG = false>
 __device__ __attribute__((always_inline)) inline void locate_correct(
     typename mfma_traits<MM>::acc_t (&acc)[FM][FN], const float (&cc)[FN],
-    const float (&cw)[FN], int sub, float tau) {
+    const float (&cw)[FN], int sub, float tau,
+    const FaultCtx& ctx = FaultCtx{}) {
   constexpr int NREG = mfma_traits<MM>::nreg;
+  bool any_bad = false;
+  if constexpr (LOG) {
+    if (__lane_id() == 0) atomicAdd(ctx.log.counters + FLOG_TRIPPED, 1);
+  }
 #pragma unroll
   for (int fn = 0; fn < FN; ++fn) {
     // fp32 screen: four independent chains (order is free here — the sum
@@ -245,6 +275,28 @@ __device__ __attribute__((always_inline)) inline void locate_correct(
     const float rw = slice_sum<MM>(colwf) - slice_sum<MM>(cw[fn]);
     const bool cbad = fabsf(rc) > tau;
     const int row = (int)rintf(rw / (cbad ? rc : 1.f));
+    if constexpr (LOG) {
+      any_bad |= __any(cbad) != 0;
+      const int lane = __lane_id();
+      if (cbad && lane < MM) {  // one reporter per column
+        const bool located = row >= 0 && row < FM * MM;
+        const int slot = atomicAdd(ctx.log.counters + FLOG_N_EVENTS, 1);
+        atomicAdd(ctx.log.counters +
+                      (located ? FLOG_CORRECTED : FLOG_UNCORRECTED), 1);
+        if (slot >= 0 && slot < ctx.log.capacity) {
+          int* ev = ctx.log.events + (size_t)slot * FLOG_EVENT_DWORDS;
+          ev[FLOG_EV_I] = located ? ctx.i0 + row : -1;
+          ev[FLOG_EV_J] = ctx.j0 + fn * MM + lane;
+          ev[FLOG_EV_K_BEGIN] = ctx.k_begin;
+          ev[FLOG_EV_K_END] = ctx.k_end;
+          ev[FLOG_EV_STATUS] =
+              located ? FLOG_STATUS_CORRECTED : FLOG_STATUS_UNCORRECTED;
+          ev[FLOG_EV_MAGNITUDE] = __float_as_int(rc);
+          ev[FLOG_EV_BAND_ROW] = ctx.i0;
+          ev[FLOG_EV_BAND_ROWS] = FM * MM;
+        }
+      }
+    }
     int sub_c = sub;  // independent opaque copy for the correct pass
     asm volatile("" : "+v"(sub_c));
 #pragma unroll
@@ -258,6 +310,10 @@ __device__ __attribute__((always_inline)) inline void locate_correct(
         acc[fm][fn][reg] -= hit ? rc : 0.f;
       }
     }
+  }
+  if constexpr (LOG) {
+    if (!any_bad && __lane_id() == 0)
+      atomicAdd(ctx.log.counters + FLOG_UNLOCATED, 1);
   }
 }
 
@@ -304,12 +360,12 @@ __global__ __launch_bounds__(256) void segsum_kernel(
 }
 
 template <int BM, int BN, int BK, int WM, int WN, int MM, bool ABFT,
-          bool INJECT, int OCC = 2>
+          bool INJECT, int OCC = 2, bool LOG = false>
 __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
     int M, int N, int K, const float* __restrict__ A,
     const float* __restrict__ B, float* __restrict__ C, float alpha,
     float beta, int verify_iters, int inject_stride, float tau, float inj_mag,
-    const float* __restrict__ SA, int sstr) {
+    const float* __restrict__ SA, int sstr, FaultLog flog) {
   using T = mfma_traits<MM>;
   constexpr int KSTEP = T::kstep;
   constexpr int NREG = T::nreg;
@@ -462,7 +518,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
   // fragment's row range nothing matches and the kernel fail-safes to
   // detected-but-uncorrected.  Faults in different columns (the common
   // double-fault shape) locate independently per lane and correct fine.
-  auto verify_correct = [&]() __attribute__((always_inline)) {
+  auto verify_correct = [&](int it_end) __attribute__((always_inline)) {
     // Cheap detect: total tile sum vs total checksum (FM*FN*NREG adds + 6
     // shuffles).  The residual is identical across the wave's lanes, so
     // the branch is uniform; only a wave that actually absorbed a fault
@@ -482,8 +538,21 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
     float res = tot - chk;
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) res += __shfl_xor(res, m, 64);
-    if (__builtin_expect(fabsf(res) > tau, 0))
-      locate_correct<FM, FN, MM>(acc, cc, cw, sub, tau);
+    if (__builtin_expect(fabsf(res) > tau, 0)) {
+      // Fault-log context, built here in the cold branch only.  it_end is
+      // the burst's end panel and bursts start at multiples of verify_iters,
+      // so the burst's first panel needs no register of its own in the loop.
+      FaultCtx ctx;
+      if constexpr (LOG) {
+        ctx.log = flog;
+        const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        ctx.i0 = im0 + (wv / WAVES_N) * WM;
+        ctx.j0 = jn0 + (wv % WAVES_N) * WN;
+        ctx.k_begin = ((it_end - 1) / verify_iters) * verify_iters * BK;
+        ctx.k_end = it_end * BK;
+      }
+      locate_correct<FM, FN, MM, LOG>(acc, cc, cw, sub, tau, ctx);
+    }
   };
 
   // ---- main K loop: one barrier per BK panel, glds prefetch overlaps ----
@@ -584,7 +653,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
         for (int kk = 0; kk < NKK; ++kk) cs.encode(swv[kk], bv[kk]);
       }
     }
-    if constexpr (ABFT) verify_correct();
+    if constexpr (ABFT) verify_correct(it);
   }
 
   // ---- epilogue: alpha/beta merge, float4 along column-major columns ----

@@ -132,13 +132,13 @@ void sk_fixup_kernel(int M, int N, int upt, int G, float alpha, float beta,
 }
 
 template <int BM, int BN, int BK, int WM, int WN, int MM, bool ABFT,
-          bool INJECT, int OCC = 2>
+          bool INJECT, int OCC = 2, bool LOG = false>
 __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC)
 void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
                         const float* __restrict__ B, float* __restrict__ C,
                         float alpha, float beta, int istride, float tau,
                         float inj_mag, const float* __restrict__ SA, int sstr,
-                        float* __restrict__ partials) {
+                        float* __restrict__ partials, FaultLog flog) {
   using T = mfma_traits<MM>;
   constexpr int KSTEP = T::kstep;
   constexpr int NREG = T::nreg;
@@ -234,7 +234,11 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
     // verify + the shared locate_correct() of csrc/ft_kernels.hpp: the
     // same detect as the classic kernel's verify_correct, operating on
     // this workgroup's PARTIAL k-range accumulation.
-    auto verify_correct = [&]() __attribute__((always_inline)) {
+    // (im0, jn0, kbase) place the segment's tile; p_end is the group's end
+    // panel within the segment and groups start at multiples of ppg panels:
+    // all the fault log needs, and only read in the tripped branch.
+    auto verify_correct = [&](int im0, int jn0, int kbase, int p_end, int ppg)
+        __attribute__((always_inline)) {
       float tot = 0.f, chk = 0.f;
       float cc[FN], cw[FN];
 #pragma unroll
@@ -250,8 +254,18 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
       float res = tot - chk;
 #pragma unroll
       for (int m = 1; m < 64; m <<= 1) res += __shfl_xor(res, m, 64);
-      if (__builtin_expect(fabsf(res) > tau, 0))
-        locate_correct<FM, FN, MM>(acc, cc, cw, sub, tau);
+      if (__builtin_expect(fabsf(res) > tau, 0)) {
+        FaultCtx ctx;
+        if constexpr (LOG) {
+          ctx.log = flog;
+          const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+          ctx.i0 = im0 + (wv / WAVES_N) * WM;
+          ctx.j0 = jn0 + (wv % WAVES_N) * WN;
+          ctx.k_begin = kbase + ((p_end - 1) / ppg) * ppg * BK;
+          ctx.k_end = kbase + p_end * BK;
+        }
+        locate_correct<FM, FN, MM, LOG>(acc, cc, cw, sub, tau, ctx);
+      }
     };
 
   while (u < u_end) {
@@ -336,7 +350,7 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
           for (int kk = 0; kk < NKK; ++kk) cs.encode(swv[kk], bv[kk]);
         }
       }
-      if constexpr (ABFT) verify_correct();
+      if constexpr (ABFT) verify_correct(im0, jn0, kbase, p, PPG);
     }
 
     // ---- tile contribution ----

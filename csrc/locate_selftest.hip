@@ -150,6 +150,81 @@ __global__ __launch_bounds__(64) void locate_selftest_kernel(
   store(1);
 }
 
+// Report variant: only the shipped locate_correct, in its fault-log (LOG)
+// form, on the same case descriptors.  Every case owns a log of its own —
+// counters + cs*FLOG_N_COUNTERS, events + cs*capacity*FLOG_EVENT_DWORDS —
+// with the wave tile at origin (0, 0) and the k range [0, 0).
+// out: [ncases][FM*FN*NREG][64], the corrected tile.
+template <int FM, int FN, int MM>
+__global__ __launch_bounds__(64) void locate_selftest_report_kernel(
+    int ncases, const int* __restrict__ idesc,
+    const float* __restrict__ fdesc, float amp, float* __restrict__ out,
+    int* __restrict__ counters, int* __restrict__ events, int capacity) {
+  using T = mfma_traits<MM>;
+  constexpr int NREG = T::nreg;
+  constexpr int E = FM * FN * NREG;
+  const int cs = blockIdx.x;
+  if (cs >= ncases) return;
+  const int lane = threadIdx.x;
+  const int sub = lane / MM;
+
+  const int* id = idesc + (size_t)cs * 9;
+  const float* fd = fdesc + (size_t)cs * 3;
+  const int nf = id[0];
+  const float tau = fd[2];
+
+  typename T::acc_t tile[FM][FN];
+  auto fill = [&](bool faulty) __attribute__((always_inline)) {
+#pragma unroll
+    for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+      for (int fn = 0; fn < FN; ++fn)
+#pragma unroll
+        for (int reg = 0; reg < NREG; ++reg) {
+          float v = hash_val(cs, (fm * FN + fn) * NREG + reg, lane, amp);
+          for (int f = 0; f < 2; ++f) {
+            const int* s = id + 1 + 4 * f;
+            if (faulty && f < nf && s[0] == fm && s[1] == fn &&
+                s[2] == reg && s[3] == lane)
+              v += fd[f];
+          }
+          tile[fm][fn][reg] = v;
+        }
+  };
+
+  // same checksum construction as locate_selftest_kernel
+  fill(false);
+  float cc[FN], cw[FN];
+#pragma unroll
+  for (int fn = 0; fn < FN; ++fn) {
+    cc[fn] = 0.f;
+    cw[fn] = 0.f;
+#pragma unroll
+    for (int fm = FM - 1; fm >= 0; --fm)
+#pragma unroll
+      for (int reg = NREG - 1; reg >= 0; --reg) {
+        const float v = tile[fm][fn][reg];
+        cc[fn] += v;
+        cw[fn] = fmaf((float)(fm * MM + acc_row(reg, sub)), v, cw[fn]);
+      }
+  }
+
+  fill(true);
+  FaultCtx ctx;
+  ctx.log.counters = counters + (size_t)cs * FLOG_N_COUNTERS;
+  ctx.log.events = events + (size_t)cs * capacity * FLOG_EVENT_DWORDS;
+  ctx.log.capacity = capacity;
+  locate_correct<FM, FN, MM, true>(tile, cc, cw, sub, tau, ctx);
+  float* o = out + (size_t)cs * E * 64 + lane;
+#pragma unroll
+  for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+    for (int fn = 0; fn < FN; ++fn)
+#pragma unroll
+      for (int reg = 0; reg < NREG; ++reg)
+        o[(size_t)((fm * FN + fn) * NREG + reg) * 64] = tile[fm][fn][reg];
+}
+
 template <int FM, int FN, int MM>
 hipError_t launch_selftest(int ncases, const int* idesc, const float* fdesc,
                            float amp, float* out, hipStream_t stream) {
@@ -158,7 +233,39 @@ hipError_t launch_selftest(int ncases, const int* idesc, const float* fdesc,
   return hipGetLastError();
 }
 
+template <int FM, int FN, int MM>
+hipError_t launch_selftest_report(int ncases, const int* idesc,
+                                  const float* fdesc, float amp, float* out,
+                                  int* counters, int* events, int capacity,
+                                  hipStream_t stream) {
+  hipLaunchKernelGGL((locate_selftest_report_kernel<FM, FN, MM>),
+                     dim3(ncases), dim3(64), 0, stream, ncases, idesc, fdesc,
+                     amp, out, counters, events, capacity);
+  return hipGetLastError();
+}
+
 }  // namespace
+
+hipError_t locate_selftest_report_launch(int fm, int fn, int mm, int ncases,
+                                         const int* idesc, const float* fdesc,
+                                         float amp, float* out, int* counters,
+                                         int* events, int capacity,
+                                         hipStream_t stream) {
+  if (ncases < 1 || capacity < 0 || !counters || (capacity > 0 && !events))
+    return hipErrorInvalidValue;
+#define FT_SELFTEST_REPORT(FM_, FN_, MM_)                                    \
+  if (fm == FM_ && fn == FN_ && mm == MM_)                                   \
+    return launch_selftest_report<FM_, FN_, MM_>(ncases, idesc, fdesc, amp,  \
+                                                 out, counters, events,      \
+                                                 capacity, stream);
+  FT_SELFTEST_REPORT(4, 2, 32)
+  FT_SELFTEST_REPORT(2, 1, 32)
+  FT_SELFTEST_REPORT(1, 2, 32)
+  FT_SELFTEST_REPORT(1, 1, 32)
+  FT_SELFTEST_REPORT(1, 1, 16)
+#undef FT_SELFTEST_REPORT
+  return hipErrorInvalidValue;
+}
 
 hipError_t locate_selftest_launch(int fm, int fn, int mm, int ncases,
                                   const int* idesc, const float* fdesc,

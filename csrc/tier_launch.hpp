@@ -80,7 +80,7 @@ hipError_t launch_tier_streamk_t(bool abft, bool inject, int M, int N, int K,
                                  const float* A, const float* B, float* C,
                                  float alpha, float beta, float tau,
                                  float inj_mag, int verify_windows, float* ws,
-                                 hipStream_t stream) {
+                                 hipStream_t stream, const FaultLog* log) {
   const int mode = streamk_env_mode();
   if (mode == 0) return hipErrorNotSupported;
   if (M % BM || N % BN || K % 64 || K % (abft ? BKF : BK) || M % 4 ||
@@ -95,6 +95,18 @@ hipError_t launch_tier_streamk_t(bool abft, bool inject, int M, int N, int K,
                      : &sgemm_mfma_streamk<BM, BN, BKF, WM, WN, MM, true,
                                            false>)
            : &sgemm_mfma_streamk<BM, BN, BK, WM, WN, MM, false, false>;
+  // The fault-log twins (LOG) of the fused variants.  The occupancy query,
+  // and with it the classic/stream-K decision and the grid G, always uses
+  // the unlogged kernel: attaching a log must not change the decomposition
+  // (and so the summation order of C).  Nothing needs G co-resident.
+  const FaultLog flog = (abft && log && log->counters) ? *log : FaultLog{};
+  const auto kfn_launch =
+      !flog.counters
+          ? kfn
+          : (inject ? &sgemm_mfma_streamk<BM, BN, BKF, WM, WN, MM, true, true,
+                                          2, true>
+                    : &sgemm_mfma_streamk<BM, BN, BKF, WM, WN, MM, true,
+                                          false, 2, true>);
   int maxblk = 0;
   const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(
       &maxblk, (const void*)kfn, THREADS, 0);
@@ -195,8 +207,9 @@ hipError_t launch_tier_streamk_t(bool abft, bool inject, int M, int N, int K,
   if (hipMallocAsync((void**)&partials, pbytes, stream) != hipSuccess)
     return hipErrorNotSupported;  // nothing mutated yet; classic path
 
-  hipLaunchKernelGGL(kfn, dim3(G), dim3(THREADS), 0, stream, M, N, K, A, B, C,
-                     alpha, beta, istride, tau, inj_mag, SA, sstr, partials);
+  hipLaunchKernelGGL(kfn_launch, dim3(G), dim3(THREADS), 0, stream, M, N, K, A,
+                     B, C, alpha, beta, istride, tau, inj_mag, SA, sstr,
+                     partials, flog);
   hipError_t err = hipGetLastError();
   if (err == hipSuccess) {
     // combine split tiles (fully-owned tiles exit immediately)
@@ -216,7 +229,8 @@ template <int BM, int BN, int BK, int BKF, int WM, int WN, int MM>
 hipError_t launch_tier(bool abft, bool inject, int M, int N, int K,
                        const float* A, const float* B, float* C, float alpha,
                        float beta, float tau, float inj_mag,
-                       int verify_windows, float* ws, hipStream_t stream) {
+                       int verify_windows, float* ws, hipStream_t stream,
+                       const FaultLog* log) {
   const int bk_used = abft ? BKF : BK;
   if (M % BM || N % BN || K % bk_used || M % 4 || N % 4)
     return hipErrorInvalidValue;
@@ -238,18 +252,32 @@ hipError_t launch_tier(bool abft, bool inject, int M, int N, int K,
   }
   RoctxRange rr_main(abft ? (inject ? "ft_sgemm_abft_inject" : "ft_sgemm_abft")
                           : "sgemm_plain");
-  if (abft && inject) {
+  // caller-owned fault log, fused variants only: no allocation, no sync, so
+  // the launch stays legal under graph capture.  With a log attached the
+  // LOG twin runs; without one, the unlogged kernel.
+  const FaultLog flog = (abft && log && log->counters) ? *log : FaultLog{};
+  if (flog.counters && inject) {
+    hipLaunchKernelGGL(
+        (sgemm_mfma<BM, BN, BKF, WM, WN, MM, true, true, 2, true>), grid,
+        block, 0, stream, M, N, K, A, B, C, alpha, beta, stride, stride, tau,
+        inj_mag, SA, sstr, flog);
+  } else if (flog.counters) {
+    hipLaunchKernelGGL(
+        (sgemm_mfma<BM, BN, BKF, WM, WN, MM, true, false, 2, true>), grid,
+        block, 0, stream, M, N, K, A, B, C, alpha, beta, stride, stride, tau,
+        inj_mag, SA, sstr, flog);
+  } else if (abft && inject) {
     hipLaunchKernelGGL((sgemm_mfma<BM, BN, BKF, WM, WN, MM, true, true>), grid,
                        block, 0, stream, M, N, K, A, B, C, alpha, beta,
-                       stride, stride, tau, inj_mag, SA, sstr);
+                       stride, stride, tau, inj_mag, SA, sstr, flog);
   } else if (abft) {
     hipLaunchKernelGGL((sgemm_mfma<BM, BN, BKF, WM, WN, MM, true, false>),
                        grid, block, 0, stream, M, N, K, A, B, C, alpha, beta,
-                       stride, stride, tau, inj_mag, SA, sstr);
+                       stride, stride, tau, inj_mag, SA, sstr, flog);
   } else {
     hipLaunchKernelGGL((sgemm_mfma<BM, BN, BK, WM, WN, MM, false, false>),
                        grid, block, 0, stream, M, N, K, A, B, C, alpha, beta,
-                       stride, stride, tau, inj_mag, SA, sstr);
+                       stride, stride, tau, inj_mag, SA, sstr, flog);
   }
   return hipGetLastError();
 }

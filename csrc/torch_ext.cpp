@@ -30,11 +30,39 @@ void check_inputs(const at::Tensor& a, const at::Tensor& b,
               "ft_sgemm: C must be (N,M) for column-major MxN");
 }
 
+// counters / events: optional fault log of the fused kernels (fault_log.h),
+// int32, contiguous, on the operands' device; events is (capacity, 8).
 void sgemm(int64_t tier, bool abft, bool inject, at::Tensor a, at::Tensor b,
            at::Tensor c, double alpha, double beta, double tau,
-           double inj_mag, int64_t verify_windows) {
+           double inj_mag, int64_t verify_windows,
+           c10::optional<at::Tensor> counters,
+           c10::optional<at::Tensor> events) {
   int64_t M, N, K;
   check_inputs(a, b, c, M, N, K);
+  TORCH_CHECK(counters.has_value() == events.has_value(),
+              "ft_sgemm: fault-log counters and events go together");
+  ftsgemm::FaultLog flog;
+  if (counters.has_value()) {
+    const at::Tensor& cn = *counters;
+    const at::Tensor& ev = *events;
+    TORCH_CHECK(abft, "ft_sgemm: a fault log needs a fused-ABFT kernel");
+    TORCH_CHECK(cn.scalar_type() == at::kInt && ev.scalar_type() == at::kInt,
+                "ft_sgemm: fault-log tensors must be int32");
+    TORCH_CHECK(cn.is_contiguous() && ev.is_contiguous(),
+                "ft_sgemm: fault-log tensors must be contiguous");
+    TORCH_CHECK(cn.device() == a.device() && ev.device() == a.device(),
+                "ft_sgemm: fault-log tensors must be on the operands' device");
+    TORCH_CHECK(cn.dim() == 1 && cn.size(0) >= ftsgemm::FLOG_N_COUNTERS,
+                "ft_sgemm: fault-log counters must hold ",
+                (int)ftsgemm::FLOG_N_COUNTERS, " int32");
+    TORCH_CHECK(ev.dim() == 2 && ev.size(1) == ftsgemm::FLOG_EVENT_DWORDS &&
+                    ev.size(0) <= (1 << 24),
+                "ft_sgemm: fault-log events must be (capacity, ",
+                (int)ftsgemm::FLOG_EVENT_DWORDS, ") int32");
+    flog.counters = cn.mutable_data_ptr<int>();
+    flog.events = ev.mutable_data_ptr<int>();
+    flog.capacity = (int)ev.size(0);
+  }
   TORCH_CHECK(ftsgemm::sgemm_tier_supported((int)tier, M, N, K),
               "ft_sgemm: tier ", tier, " requires M,N,K multiples of its "
               "tile (M=", M, " N=", N, " K=", K, ")");
@@ -52,7 +80,8 @@ void sgemm(int64_t tier, bool abft, bool inject, at::Tensor a, at::Tensor b,
       (int)tier, abft, inject, (int)M, (int)N, (int)K,
       a.const_data_ptr<float>(), b.const_data_ptr<float>(),
       c.mutable_data_ptr<float>(), (float)alpha, (float)beta, (float)tau,
-      (float)inj_mag, (int)verify_windows, ws_ptr, stream.stream());
+      (float)inj_mag, (int)verify_windows, ws_ptr, stream.stream(),
+      flog.counters ? &flog : nullptr);
   TORCH_CHECK(err == hipSuccess,
               "ft_sgemm launch failed: ", hipGetErrorString(err));
 }
@@ -132,13 +161,58 @@ at::Tensor locate_selftest(int64_t fm, int64_t fn, int64_t mm,
   return out;
 }
 
+// Report variant: (corrected tiles (ncases, fm*fn*nreg, 64), counters
+// (ncases, 5) int32, events (ncases, capacity, 8) int32), one log per case.
+std::tuple<at::Tensor, at::Tensor, at::Tensor> locate_selftest_report(
+    int64_t fm, int64_t fn, int64_t mm, at::Tensor idesc, at::Tensor fdesc,
+    double amp, int64_t capacity) {
+  TORCH_CHECK(idesc.is_cuda() && fdesc.is_cuda(),
+              "locate_selftest_report: descriptors must be on a GPU device");
+  TORCH_CHECK(idesc.scalar_type() == at::kInt && idesc.is_contiguous() &&
+                  idesc.dim() == 2 && idesc.size(1) == 9,
+              "locate_selftest_report: idesc must be contiguous int32 "
+              "(ncases, 9)");
+  const int64_t ncases = idesc.size(0);
+  TORCH_CHECK(fdesc.scalar_type() == at::kFloat && fdesc.is_contiguous() &&
+                  fdesc.dim() == 2 && fdesc.size(0) == ncases &&
+                  fdesc.size(1) == 3,
+              "locate_selftest_report: fdesc must be contiguous fp32 "
+              "(ncases, 3)");
+  TORCH_CHECK(ncases >= 1 && ncases <= (1 << 20),
+              "locate_selftest_report: 1..2^20 cases");
+  TORCH_CHECK(capacity >= 1 && capacity <= 1024,
+              "locate_selftest_report: capacity 1..1024");
+  const int64_t nreg = mm == 32 ? 16 : 4;
+  at::Tensor out = at::empty({ncases, fm * fn * nreg, 64}, fdesc.options());
+  at::Tensor counters =
+      at::zeros({ncases, ftsgemm::FLOG_N_COUNTERS}, idesc.options());
+  at::Tensor events = at::zeros(
+      {ncases, capacity, ftsgemm::FLOG_EVENT_DWORDS}, idesc.options());
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipError_t err = ftsgemm::locate_selftest_report_launch(
+      (int)fm, (int)fn, (int)mm, (int)ncases, idesc.const_data_ptr<int>(),
+      fdesc.const_data_ptr<float>(), (float)amp,
+      out.mutable_data_ptr<float>(), counters.mutable_data_ptr<int>(),
+      events.mutable_data_ptr<int>(), (int)capacity, stream.stream());
+  TORCH_CHECK(err == hipSuccess,
+              "locate_selftest_report: unsupported (fm, fn, mm) or launch "
+              "failure: ", hipGetErrorString(err));
+  return {out, counters, events};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-  m.def("sgemm", &sgemm, "tiered MFMA SGEMM (column-major C=aAB^T+bC)");
+  m.def("sgemm", &sgemm, "tiered MFMA SGEMM (column-major C=aAB^T+bC)",
+        py::arg("tier"), py::arg("abft"), py::arg("inject"), py::arg("a"),
+        py::arg("b"), py::arg("c"), py::arg("alpha"), py::arg("beta"),
+        py::arg("tau"), py::arg("inj_mag"), py::arg("verify_windows"),
+        py::arg("counters") = py::none(), py::arg("events") = py::none());
   m.def("rocblas_sgemm", &rocblas_sgemm_nt, "rocBLAS oracle SGEMM");
   m.def("baseline_ft", &baseline_ft, "non-fused rocBLAS ABFT baseline");
   m.def("tier_supported", &tier_supported, "tile divisibility check");
   m.def("locate_selftest", &locate_selftest,
         "device self-test of the ABFT locate/correct");
+  m.def("locate_selftest_report", &locate_selftest_report,
+        "self-test of the shipped locate/correct with a fault log per case");
 }

@@ -26,6 +26,18 @@ ops.sgemm("huge", a, b, c, alpha=1.0, beta=0.0)
 #    still matches the clean product
 ops.ft_sgemm("huge", a, b, c, alpha=1.0, beta=0.0, inject=True)
 
+# 2b. the same, with a fault report: which element, which k window, was it
+#     corrected.  A report accumulates across launches until reset();
+#     read() is the only call that synchronises.
+report = ops.FaultReport(capacity=1024)
+ops.ft_sgemm("huge", a, b, c, alpha=1.0, beta=0.0, inject=True, report=report)
+r = report.read()
+print(f"faults: tripped {r.tripped} corrected {r.corrected} uncorrected "
+      f"{r.uncorrected} unlocated {r.unlocated} (dropped {r.dropped})")
+print("first event:", r.events[0])
+report.raise_if_uncorrected()   # refuse a result that could not be repaired
+report.reset()
+
 # 3. automatic tier selection (grid-fill aware)
 ops.ft_sgemm_auto(a, b, c)
 

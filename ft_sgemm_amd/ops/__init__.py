@@ -12,6 +12,8 @@ import torch
 
 from ..kernel_table import (ERR_BOUND, ERROR_INJECT, KERNEL_TABLE, TIERS)
 from . import golden  # noqa: F401
+from .fault_report import (FaultCounts, FaultEvent, FaultReport,  # noqa: F401
+                           predict_injected_events)
 
 _C = None
 _load_err = None
@@ -50,12 +52,25 @@ def sgemm(tier: str, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
 def ft_sgemm(tier: str, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
              alpha: float = 1.0, beta: float = 0.0, inject: bool = True,
              tau: float = ERR_BOUND, inj_mag: float = ERROR_INJECT,
-             verify_windows: int = 20) -> torch.Tensor:
+             verify_windows: int = 20,
+             report: FaultReport | None = None) -> torch.Tensor:
     """Fused-ABFT MFMA SGEMM with in-kernel verify/locate/correct.  The
     default inject=True preserves the reference's always-self-testing
-    property."""
-    _require_ext().sgemm(tier_index(tier), True, inject, a, b, c,
-                         alpha, beta, tau, inj_mag, verify_windows)
+    property.
+
+    report: a FaultReport on the operands' device.  The kernel adds every
+    fault it detects to it (tripped / corrected / uncorrected / unlocated
+    counts and one event per fault); nothing is zeroed, so a report
+    accumulates across launches until report.reset().  The launch does not
+    synchronise; report.read() does.  C is bit-identical with and without
+    a report."""
+    if report is None:
+        _require_ext().sgemm(tier_index(tier), True, inject, a, b, c,
+                             alpha, beta, tau, inj_mag, verify_windows)
+    else:
+        _require_ext().sgemm(tier_index(tier), True, inject, a, b, c,
+                             alpha, beta, tau, inj_mag, verify_windows,
+                             report.counters, report.events)
     return c
 
 
@@ -70,6 +85,18 @@ def baseline_ft(a, b, c, alpha: float = 1.0, beta: float = 0.0,
     """Kernel id 10: non-fused rocBLAS ABFT chain.  Returns (c, verdicts)."""
     res = _require_ext().baseline_ft(a, b, c, alpha, beta, panel_k)
     return c, res
+
+
+def locate_selftest_report(fm: int, fn: int, mm: int, idesc: torch.Tensor,
+                           fdesc: torch.Tensor, amp: float,
+                           capacity: int = 4):
+    """locate_selftest's report twin: runs only the shipped locate/correct,
+    with a fault log per case (wave tile at origin (0, 0), k range [0, 0)),
+    on the same descriptors.  Returns (tiles (ncases, fm*fn*nreg, 64),
+    counters (ncases, 5) int32, events (ncases, capacity, 8) int32);
+    fault_report.decode(counters[c], events[c]) decodes one case."""
+    return _require_ext().locate_selftest_report(fm, fn, mm, idesc, fdesc,
+                                                 amp, capacity)
 
 
 def locate_selftest(fm: int, fn: int, mm: int, idesc: torch.Tensor,
@@ -125,13 +152,18 @@ def sgemm_auto(a, b, c, alpha: float = 1.0, beta: float = 0.0):
 
 
 def ft_sgemm_auto(a, b, c, alpha: float = 1.0, beta: float = 0.0,
-                  inject: bool = True):
+                  inject: bool = True, report: FaultReport | None = None):
     """Fused-ABFT SGEMM with automatic tier selection.  Shapes no tier
     divides fall back to the rocBLAS GEMM wrapped in the OFFLINE checksum
     ABFT chain (kernel id 10 semantics: detection verdicts, no in-kernel
     correction — the strongest FT available without a tile fit); a verdict
     above the threshold raises, making silent corruption impossible on the
-    fallback path."""
+    fallback path.
+
+    report: passed to ft_sgemm when a tier fits.  On the rocBLAS fallback
+    branch the report is left untouched: that branch has no in-kernel
+    locate/correct to report on, and it already raises on a tripped
+    verdict."""
     k, m = a.shape
     n = b.shape[1]
     tier = choose_tier(m, n, k)
@@ -146,20 +178,26 @@ def ft_sgemm_auto(a, b, c, alpha: float = 1.0, beta: float = 0.0,
                 f"(res_row={res_row:.3e}, res_col={res_col:.3e}) — "
                 f"uncorrectable fault in the rocBLAS fallback GEMM")
         return c
-    return ft_sgemm(tier, a, b, c, alpha, beta, inject=inject)
+    return ft_sgemm(tier, a, b, c, alpha, beta, inject=inject, report=report)
 
 
 def run_kernel_id(kid: int, a, b, c, alpha: float = 1.0, beta: float = 0.0,
-                  inject: bool = True):
+                  inject: bool = True, report: FaultReport | None = None):
     """Dispatch by reference kernel id (0=rocBLAS, 1-6 plain tiers,
-    7-9 rocBLAS fallback, 10 baseline, 11-16 fused-ABFT tiers)."""
+    7-9 rocBLAS fallback, 10 baseline, 11-16 fused-ABFT tiers).  `report`
+    is accepted for the fused ids only."""
+    if report is not None and not (kid in KERNEL_TABLE and
+                                   KERNEL_TABLE[kid][2]):
+        raise ValueError(f"kernel id {kid} has no fault report "
+                         f"(fused-ABFT ids 11-16 only)")
     if kid in (0, 7, 8, 9):
         return rocblas_sgemm(a, b, c, alpha, beta)
     if kid == 10:
         return baseline_ft(a, b, c, alpha, beta)[0]
     name, tier, fused = KERNEL_TABLE[kid]
     if fused:
-        return ft_sgemm(tier, a, b, c, alpha, beta, inject=inject)
+        return ft_sgemm(tier, a, b, c, alpha, beta, inject=inject,
+                        report=report)
     return sgemm(tier, a, b, c, alpha, beta)
 
 

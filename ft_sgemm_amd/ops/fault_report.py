@@ -1,0 +1,155 @@
+"""Fault report of the fused-ABFT kernels.
+
+The fused kernels detect, locate and correct accumulator faults in
+registers.  A FaultReport is the caller-owned log they fill while doing so
+(layout: csrc/fault_log.h): counters, and one event per detected fault with
+the element of C, the k range the fault was absorbed in, whether it could be
+corrected, and the magnitude that was (or would have been) subtracted.
+
+predict_injected_events() is the executable specification of what the
+classic kernel's deterministic injector must produce; it runs on the CPU.
+"""
+
+from __future__ import annotations
+
+import struct
+from dataclasses import dataclass, field
+from typing import List, NamedTuple
+
+import torch
+
+from ..kernel_table import ERROR_INJECT, TILING, threads
+
+# csrc/fault_log.h
+N_COUNTERS = 5
+(C_N_EVENTS, C_TRIPPED, C_CORRECTED, C_UNCORRECTED, C_UNLOCATED) = range(5)
+EVENT_DWORDS = 8
+STATUS_CORRECTED = 1
+STATUS_UNCORRECTED = 2
+
+
+class FaultEvent(NamedTuple):
+    """One detected fault.  (i, j) is the element of C (column-major M x N:
+    row i, column j); for an uncorrected fault no row is known, i is -1 and
+    the fault lies in rows [band_row, band_row + band_rows) of column j."""
+    i: int
+    j: int
+    k_begin: int
+    k_end: int
+    status: int
+    magnitude: float
+    band_row: int
+    band_rows: int
+
+    @property
+    def corrected(self) -> bool:
+        return self.status == STATUS_CORRECTED
+
+
+@dataclass
+class FaultCounts:
+    """Host snapshot of a FaultReport."""
+    tripped: int = 0      # waves whose verify tripped
+    corrected: int = 0    # faults located and corrected
+    uncorrected: int = 0  # faults detected whose row fell outside the tile
+    unlocated: int = 0    # tripped verifies in which no column was bad
+    dropped: int = 0      # events beyond the report's capacity
+    n_events: int = 0     # corrected + uncorrected, dropped ones included
+    events: List[FaultEvent] = field(default_factory=list)
+
+
+def _bits_to_float(v: int) -> float:
+    return struct.unpack("<f", struct.pack("<i", v))[0]
+
+
+def decode(counters: torch.Tensor, events: torch.Tensor) -> FaultCounts:
+    """Decode a raw (counters, events) pair; one device->host copy each."""
+    cnt = counters.to("cpu").tolist()
+    capacity = events.shape[0]
+    n = cnt[C_N_EVENTS]
+    rows = events[:max(0, min(n, capacity))].to("cpu").tolist()
+    evs = [FaultEvent(r[0], r[1], r[2], r[3], r[4], _bits_to_float(r[5]),
+                      r[6], r[7]) for r in rows]
+    evs.sort(key=lambda e: (e.i, e.j, e.k_begin))
+    return FaultCounts(tripped=cnt[C_TRIPPED], corrected=cnt[C_CORRECTED],
+                       uncorrected=cnt[C_UNCORRECTED],
+                       unlocated=cnt[C_UNLOCATED],
+                       dropped=max(0, n - capacity), n_events=n, events=evs)
+
+
+class FaultReport:
+    """Caller-owned fault log for ops.ft_sgemm(..., report=...).
+
+    Owns the two int32 device tensors the kernels write.  A report
+    accumulates across launches until reset(); when more than `capacity`
+    events arrive the extra ones are counted (read().dropped) but not kept.
+    """
+
+    def __init__(self, capacity: int = 1024, device="cuda"):
+        if capacity < 1:
+            raise ValueError("FaultReport: capacity must be >= 1")
+        self.capacity = int(capacity)
+        self.counters = torch.zeros(N_COUNTERS, dtype=torch.int32,
+                                    device=device)
+        self.events = torch.zeros((self.capacity, EVENT_DWORDS),
+                                  dtype=torch.int32, device=device)
+
+    def reset(self) -> None:
+        """Zero the log on the device, in stream order (no host sync)."""
+        self.counters.zero_()
+        self.events.zero_()
+
+    def read(self) -> FaultCounts:
+        """Synchronise once and return the counts and the sorted events."""
+        if self.counters.is_cuda:
+            torch.cuda.synchronize(self.counters.device)
+        return decode(self.counters, self.events)
+
+    def raise_if_uncorrected(self) -> None:
+        """Refuse a result that could not be repaired."""
+        r = self.read()
+        if r.uncorrected or r.unlocated:
+            raise RuntimeError(
+                f"fused ABFT: {r.uncorrected} uncorrected and {r.unlocated} "
+                f"unlocated fault(s) of {r.tripped} tripped verifies — the "
+                f"result holds corruption that was detected but not repaired")
+
+
+def predict_injected_events(tier: str, m: int, n: int, k: int,
+                            verify_windows: int = 20) -> List[FaultEvent]:
+    """The exact events the classic fused kernel's injector must produce for
+    an (m, n, k) GEMM on `tier`, sorted by (i, j, k_begin).
+
+    Derived from csrc/tier_launch.hpp (launch_tier: window stride) and
+    csrc/ft_kernels.hpp (sgemm_mfma: victim rotation, MFMA accumulator
+    layout): every block injects once per verify window w into
+    acc[0][0][0] of thread (w * 67) % THREADS.
+    """
+    t = TILING[tier]
+    bm, bn, wm, wn = t["bm"], t["bn"], t["wm"], t["wn"]
+    bkf = t.get("bkf", t["bk"])
+    mm = 16 if t["mfma"] == "f32_16x16x4" else 32
+    if m % bm or n % bn or k % bkf:
+        raise ValueError(f"shape ({m}, {n}, {k}) does not divide tier {tier}")
+    nthreads = threads(tier)
+    waves_n = bn // wn
+    niter = k // bkf
+    stride = max(1, niter // (verify_windows if verify_windows > 0 else 20))
+    nwin = -(-niter // stride)
+    out = []
+    for bx in range(m // bm):
+        for by in range(n // bn):
+            for w in range(nwin):
+                tid = (w * 67) % nthreads
+                wave, lane = tid >> 6, tid & 63
+                sub, r = lane // mm, lane % mm
+                out.append(FaultEvent(
+                    i=bx * bm + (wave // waves_n) * wm + 4 * sub,
+                    j=by * bn + (wave % waves_n) * wn + r,
+                    k_begin=w * stride * bkf,
+                    k_end=min((w + 1) * stride, niter) * bkf,
+                    status=STATUS_CORRECTED, magnitude=ERROR_INJECT,
+                    band_row=bx * bm + (wave // waves_n) * wm,
+                    band_rows=wm))
+    out.sort(key=lambda e: (e.i, e.j, e.k_begin))
+    return out
