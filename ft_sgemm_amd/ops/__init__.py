@@ -13,7 +13,8 @@ import torch
 from ..kernel_table import (ERR_BOUND, ERROR_INJECT, KERNEL_TABLE, TIERS)
 from . import golden  # noqa: F401
 from .fault_report import (FaultCounts, FaultEvent, FaultReport,  # noqa: F401
-                           predict_injected_events)
+                           InjectionModel, predict_injected_events,
+                           predict_injection_model)
 
 _C = None
 _load_err = None

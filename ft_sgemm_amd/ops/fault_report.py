@@ -8,6 +8,8 @@ corrected, and the magnitude that was (or would have been) subtracted.
 
 predict_injected_events() is the executable specification of what the
 classic kernel's deterministic injector must produce; it runs on the CPU.
+predict_injection_model() follows the same injections through the verify
+threshold: what trips, what is corrected, and what stays in C.
 """
 
 from __future__ import annotations
@@ -153,3 +155,106 @@ def predict_injected_events(tier: str, m: int, n: int, k: int,
                     band_rows=wm))
     out.sort(key=lambda e: (e.i, e.j, e.k_begin))
     return out
+
+
+class InjectionModel(NamedTuple):
+    """What the classic fused kernel must do with its injector's faults for
+    a given (tau, inj_mag); see predict_injection_model."""
+    mult: torch.Tensor     # (m, n) int32: injections per element of C
+    residue: torch.Tensor  # (m, n) fp64: injected magnitude left in the
+    #                        accumulators (before the alpha/beta epilogue)
+    tripped: int           # verifies whose wave residual exceeded tau
+    corrected: int
+    uncorrected: int
+    unlocated: int         # tripped verifies in which no column was bad
+    n_faults: int          # corrected + uncorrected: the event count
+    wave_totals: dict      # (bx, by, wave) -> peak |running residual|
+    col_totals: dict       # (bx, by, wave, column) -> peak |running residual|
+
+
+def predict_injection_model(tier: str, m: int, n: int, k: int, tau: float,
+                            inj_mag: float,
+                            verify_windows: int = 20) -> InjectionModel:
+    """CPU model of inject -> verify -> locate -> correct in the classic
+    fused kernel, from the same rotation rule as predict_injected_events.
+
+    Every block injects inj_mag once per verify window w into acc[0][0][0]
+    of thread (w * 67) % THREADS; at the end of each window every wave
+    compares its whole tile's residual (the running total of what was
+    injected into it and not corrected yet) against tau.  A wave that trips
+    looks at each of its columns: a column whose own total exceeds tau is a
+    fault of that magnitude at row round(sum(row * e) / sum(e)), corrected
+    when that row lies in the wave tile; when no column exceeds tau the
+    verify is counted as unlocated and the accumulators stay as they are.
+    Roundoff (orders of magnitude below any tau in use) is not modelled.
+    """
+    t = TILING[tier]
+    bm, bn, wm, wn = t["bm"], t["bn"], t["wm"], t["wn"]
+    bkf = t.get("bkf", t["bk"])
+    mm = 16 if t["mfma"] == "f32_16x16x4" else 32
+    if m % bm or n % bn or k % bkf:
+        raise ValueError(f"shape ({m}, {n}, {k}) does not divide tier {tier}")
+    nthreads = threads(tier)
+    nwaves = nthreads // 64
+    waves_n = bn // wn
+    niter = k // bkf
+    stride = max(1, niter // (verify_windows if verify_windows > 0 else 20))
+    nwin = -(-niter // stride)
+    tripped = corrected = uncorrected = unlocated = 0
+    wave_totals, col_totals = {}, {}
+    # one block's history is every block's: simulate one, then tile it
+    pending = [dict() for _ in range(nwaves)]  # col -> {row: magnitude}
+    bmult = torch.zeros((bm, bn), dtype=torch.int32)
+    wave_peak = [0.0] * nwaves
+    col_peak = {}
+    for w in range(nwin):
+        tid = (w * 67) % nthreads
+        wave, lane = tid >> 6, tid & 63
+        row, col = 4 * (lane // mm), lane % mm
+        rows = pending[wave].setdefault(col, {})
+        rows[row] = rows.get(row, 0.0) + inj_mag
+        bmult[(wave // waves_n) * wm + row, (wave % waves_n) * wn + col] += 1
+        for wv in range(nwaves):
+            total = sum(sum(r.values()) for r in pending[wv].values())
+            wave_peak[wv] = max(wave_peak[wv], abs(total))
+            for c, r in pending[wv].items():
+                key = (wv, c)
+                col_peak[key] = max(col_peak.get(key, 0.0),
+                                    abs(sum(r.values())))
+            if not abs(total) > tau:
+                continue
+            tripped += 1
+            any_bad = False
+            for c, r in pending[wv].items():
+                rc = sum(r.values())
+                if not abs(rc) > tau:
+                    continue
+                any_bad = True
+                at = int(round(sum(i * e for i, e in r.items()) / rc))
+                if 0 <= at < wm:
+                    corrected += 1
+                    r[at] = r.get(at, 0.0) - rc
+                else:
+                    uncorrected += 1
+            if not any_bad:
+                unlocated += 1
+    bres = torch.zeros((bm, bn), dtype=torch.float64)
+    for wv in range(nwaves):
+        for c, r in pending[wv].items():
+            for i, e in r.items():
+                bres[(wv // waves_n) * wm + i, (wv % waves_n) * wn + c] += e
+    nblk = (m // bm) * (n // bn)
+    mult = bmult.repeat(m // bm, n // bn)
+    residue = bres.repeat(m // bm, n // bn)
+    for bx in range(m // bm):
+        for by in range(n // bn):
+            for wv in range(nwaves):
+                wave_totals[(bx, by, wv)] = wave_peak[wv]
+            for (wv, c), v in col_peak.items():
+                col_totals[(bx, by, wv, c)] = v
+    return InjectionModel(mult=mult, residue=residue,
+                          tripped=tripped * nblk, corrected=corrected * nblk,
+                          uncorrected=uncorrected * nblk,
+                          unlocated=unlocated * nblk,
+                          n_faults=(corrected + uncorrected) * nblk,
+                          wave_totals=wave_totals, col_totals=col_totals)

@@ -125,5 +125,11 @@ def block_row_sgemm(a_local: torch.Tensor, b_local: torch.Tensor,
 
 def torch_gemm_fn(a_panel, b_panel, c_local, alpha, beta):
     """CPU/GPU plain fp32 panel GEMM for the distributed path (reference
-    implementation; the GPU fast path passes ops.ft_sgemm instead)."""
-    c_local.mul_(beta).add_(alpha * (b_panel.transpose(0, 1) @ a_panel))
+    implementation; the GPU fast path passes ops.ft_sgemm instead).  Like
+    the kernels, beta == 0 overwrites C without reading it (0 * NaN would
+    keep a NaN of an uninitialised C)."""
+    prod = alpha * (b_panel.transpose(0, 1) @ a_panel)
+    if beta == 0:
+        c_local.copy_(prod)
+    else:
+        c_local.mul_(beta).add_(prod)
