@@ -54,6 +54,15 @@ hipError_t locate_selftest_report_launch(int fm, int fn, int mm, int ncases,
                                          int* events, int capacity,
                                          hipStream_t stream);
 
+// Detect variant of the self-test: runs only the fused kernels' shared
+// detect and the locate's fp32 screen on the same descriptors, and returns
+// what they computed.  out: [ncases][FM*FN*NREG + 1 + 2*FN][64] floats, lane
+// fastest: the faulty tile, the wave residual, per fn the lane's partial
+// sum p[fn], per fn 1.0 / 0.0 for a screen that passed / did not.
+hipError_t detect_selftest_launch(int fm, int fn, int mm, int ncases,
+                                  const int* idesc, const float* fdesc,
+                                  float amp, float* out, hipStream_t stream);
+
 // rocBLAS paths (kernel id 0 oracle and the id-10 non-fused ABFT baseline,
 // reference: cuBLAS at sgemm.cu:108 / include/baseline_ft_sgemm.cuh).
 // Implemented in rocblas_path.hip.

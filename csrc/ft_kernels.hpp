@@ -177,19 +177,91 @@ struct FaultCtx {
   int i0 = 0, j0 = 0, k_begin = 0, k_end = 0;
 };
 
+// Cheap detect of one wave tile, shared by the classic and the stream-K
+// kernel (and run every verify window by every wave): compares the total
+// tile sum against the total checksum.  Returns the wave-uniform residual
+// and hands out p[fn], this lane's fp32 sum over fm and reg of
+// acc[fm][fn][reg], which locate_correct screens the fragment columns with
+// instead of sweeping them again.  The order of these sums is free: res and
+// p only gate branches and never reach C.  Per fn two independent chains of
+// packed adds run over the accumulators' own aligned register pairs (0,1),
+// (2,3), ..., so every step is a v_pk_add_f32 on registers as they lie, with
+// no move to build an operand, and FN * 2 chains are in flight instead of one
+// FM*FN*NREG-deep scalar chain (docs/ABLATION.md §5d).
+template <int FM, int FN, int MM>
+__device__ __attribute__((always_inline)) inline float detect_partials(
+    const typename mfma_traits<MM>::acc_t (&acc)[FM][FN],
+    const float (&cc)[FN], float (&p)[FN]) {
+  constexpr int NREG = mfma_traits<MM>::nreg;
+  constexpr int PPF = NREG / 2;  // register pairs per fragment
+  constexpr int NP = FM * PPF;   // register pairs per fragment column
+  static_assert(NP % 2 == 0, "two chains of whole register pairs");
+  // The residual is formed from the pair sums, not from p: p[fn] is then
+  // only read in the tripped branch, and its two halves are folded there.
+  // With FN even the checksums leave as the pairs (cc[2j], cc[2j+1]) they
+  // are kept in (checksum_regs), one packed subtract each; scalar adds of
+  // them next to the fold of tot were packed through three v_mov_b32.
+  f32x2 tot;
+#pragma unroll
+  for (int fn = 0; fn < FN; ++fn) {
+    f32x2 s[2];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+      const typename mfma_traits<MM>::acc_t& a = acc[i / PPF][fn];
+      const int reg = 2 * (i % PPF);
+      const f32x2 v{a[reg], a[reg + 1]};
+      s[i & 1] = i < 2 ? v : s[i & 1] + v;
+    }
+    const f32x2 t = s[0] + s[1];
+    p[fn] = t[0] + t[1];
+    tot = fn == 0 ? t : tot + t;
+  }
+  float res;
+  if constexpr (FN % 2 == 0) {
+#pragma unroll
+    for (int j = 0; j < FN / 2; ++j) tot -= f32x2{cc[2 * j], cc[2 * j + 1]};
+    res = tot[0] + tot[1];
+  } else {
+    res = tot[0];
+#pragma unroll
+    for (int fn = 0; fn < FN; ++fn) res -= cc[fn];
+    res += tot[1];
+  }
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) res += __shfl_xor(res, m, 64);
+  return res;
+}
+
+// The fp32 screen of one fragment column, from the detect's partial p and
+// this lane's checksum partial cc: wave-uniform, true when some lane's column
+// residual exceeds tau/2.  The exact decision in locate_correct is |rc| > tau
+// on the fp64 sum; the two residuals differ by the fp32 rounding of FM*NREG
+// terms (~1e-2 at the |acc| ~ 1e4 of a faulty column), orders of magnitude
+// below the tau/2 margin, so the screen passes a strict superset.
+template <int MM>
+__device__ __attribute__((always_inline)) inline bool screen_passes(
+    float p, float cc, float tau) {
+  const float rc32 = slice_sum<MM>(p - cc);
+  // Opaque copy of tau for the screen only.  Measured, not reasoned:
+  // without it the K-panel loop of the huge no-injection kernel is
+  // scheduled slightly differently and runs 0.6% slower; with it the
+  // loop is nearly the unscreened kernel's (docs/ABLATION.md §5a).
+  float tau_o = tau;
+  asm volatile("" : "+v"(tau_o));
+  return __any(fabsf(rc32) > 0.5f * tau_o) != 0;
+}
+
 // ABFT ratio locate + in-register correct of one wave tile, shared by the
 // classic and the stream-K kernel (entered only after the cheap detect in
 // their verify_correct tripped; the scheme itself is described there).
 // acc[FM][FN] is the wave's accumulator tile, cc/cw this lane's plain and
-// row-weighted column-checksum partials, sub = lane / MM.
+// row-weighted column-checksum partials, p the per-fn partial sums the
+// detect (detect_partials) just formed of the same acc, sub = lane / MM.
 //
 // Only the work a fault needs is done:
-//   * per fn, an fp32 SCREEN of the column residual (|rc32| > tau/2 in any
-//     lane, wave-uniform) decides whether the fragment column is looked at
-//     at all.  The exact decision below is |rc| > tau on the fp64 sum; the
-//     two residuals differ by the fp32 rounding of FM*NREG terms (~1e-2 at
-//     the |acc| ~ 1e4 of a faulty column), orders of magnitude below the
-//     tau/2 margin, so the screen passes a strict superset.
+//   * per fn, an fp32 SCREEN of the column residual (screen_passes, on the
+//     detect's p[fn]: the column is not summed a second time) decides
+//     whether the fragment column is looked at at all.
 //   * per fm, the correction sweep runs only for a fragment some lane
 //     located its row in.
 // The arithmetic on a column that IS processed is the unscreened one, in
@@ -211,7 +283,7 @@ struct FaultCtx {
 template <int FM, int FN, int MM, bool LOG = false>
 __device__ __attribute__((always_inline)) inline void locate_correct(
     typename mfma_traits<MM>::acc_t (&acc)[FM][FN], const float (&cc)[FN],
-    const float (&cw)[FN], int sub, float tau,
+    const float (&cw)[FN], const float (&p)[FN], int sub, float tau,
     const FaultCtx& ctx = FaultCtx{}) {
   constexpr int NREG = mfma_traits<MM>::nreg;
   bool any_bad = false;
@@ -220,26 +292,11 @@ __device__ __attribute__((always_inline)) inline void locate_correct(
   }
 #pragma unroll
   for (int fn = 0; fn < FN; ++fn) {
-    // fp32 screen: four independent chains (order is free here — the sum
-    // only gates the branch, it never reaches the output)
     // With a single fragment column (FN == 1) the tripped detect already
     // says the fault is in it: no screen (it would only add code — and on
     // the tall tier two VGPRs that cost a wave of occupancy).
     if constexpr (FN > 1) {
-      float p[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-        for (int reg = 0; reg < NREG; ++reg) p[reg & 3] += acc[fm][fn][reg];
-      const float rc32 = slice_sum<MM>((p[0] + p[1]) + (p[2] + p[3])) -
-                         slice_sum<MM>(cc[fn]);
-      // Opaque copy of tau for the screen only.  Measured, not reasoned:
-      // without it the K-panel loop of the huge no-injection kernel is
-      // scheduled slightly differently and runs 0.6% slower; with it the
-      // loop is nearly the unscreened kernel's (docs/ABLATION.md §5a).
-      float tau_o = tau;
-      asm volatile("" : "+v"(tau_o));
-      if (!__any(fabsf(rc32) > 0.5f * tau_o)) continue;
+      if (!screen_passes<MM>(p[fn], cc[fn], tau)) continue;
     }
 
     // fp64 PLAIN column sum: the fault itself (|e| ~ 1e4) sits in this
@@ -258,8 +315,15 @@ __device__ __attribute__((always_inline)) inline void locate_correct(
     // kernel prologue and keeps them live through the whole hot loop
     // (+68 VGPRs measured on the 64x64-wave tile -> spills on the bigger
     // tiles).
+    //
+    // A row weight is fm*MM + acc_row(reg, 0), a compile-time constant,
+    // plus 4*sub.  The lane's part is turned into a float ONCE; each weight
+    // is then one fp32 add of a literal — exact, all are integers below
+    // 2^24, so the very float the integer sum + conversion gave and rw
+    // keeps its bits — instead of an integer add and a conversion per term.
     int sub_o = sub;  // fresh opaque copy per fn: stops the
     asm volatile("" : "+v"(sub_o));  // weights being CSE'd+spilled
+    const float row0 = (float)acc_row(0, sub_o);  // 4 * sub
     double colp = 0.0;
     float colwf = 0.f;
 #pragma unroll
@@ -268,7 +332,7 @@ __device__ __attribute__((always_inline)) inline void locate_correct(
       for (int reg = 0; reg < NREG; ++reg) {
         const float v = acc[fm][fn][reg];
         colp += (double)v;
-        colwf = fmaf((float)(fm * MM + acc_row(reg, sub_o)), v, colwf);
+        colwf = fmaf((float)(fm * MM + acc_row(reg, 0)) + row0, v, colwf);
       }
     const float rc =
         (float)(dslice_sum<MM>(colp) - (double)slice_sum<MM>(cc[fn]));
@@ -519,25 +583,17 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
   // detected-but-uncorrected.  Faults in different columns (the common
   // double-fault shape) locate independently per lane and correct fine.
   auto verify_correct = [&](int it_end) __attribute__((always_inline)) {
-    // Cheap detect: total tile sum vs total checksum (FM*FN*NREG adds + 6
-    // shuffles).  The residual is identical across the wave's lanes, so
+    // Cheap detect (detect_partials, above): total tile sum vs total
+    // checksum.  The residual is identical across the wave's lanes, so
     // the branch is uniform; only a wave that actually absorbed a fault
-    // enters locate_correct().
-    float tot = 0.f, chk = 0.f;
-    float cc[FN], cw[FN];
+    // enters locate_correct(), which gets the detect's per-fn partials.
+    float cc[FN], cw[FN], p[FN];
 #pragma unroll
     for (int fn = 0; fn < FN; ++fn) {
       cc[fn] = cs.cc(fn);
       cw[fn] = cs.cw(fn);
-      chk += cc[fn];
-#pragma unroll
-      for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-        for (int reg = 0; reg < NREG; ++reg) tot += acc[fm][fn][reg];
     }
-    float res = tot - chk;
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) res += __shfl_xor(res, m, 64);
+    const float res = detect_partials<FM, FN, MM>(acc, cc, p);
     if (__builtin_expect(fabsf(res) > tau, 0)) {
       // Fault-log context, built here in the cold branch only.  it_end is
       // the burst's end panel and bursts start at multiples of verify_iters,
@@ -551,7 +607,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
         ctx.k_begin = ((it_end - 1) / verify_iters) * verify_iters * BK;
         ctx.k_end = it_end * BK;
       }
-      locate_correct<FM, FN, MM, LOG>(acc, cc, cw, sub, tau, ctx);
+      locate_correct<FM, FN, MM, LOG>(acc, cc, cw, p, sub, tau, ctx);
     }
   };
 

@@ -231,29 +231,21 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
     for (int fn = 0; fn < FN; ++fn) acc[fm][fn] = {};
   cs.clear();
 
-    // verify + the shared locate_correct() of csrc/ft_kernels.hpp: the
-    // same detect as the classic kernel's verify_correct, operating on
-    // this workgroup's PARTIAL k-range accumulation.
+    // verify: the shared detect_partials() and locate_correct() of
+    // csrc/ft_kernels.hpp, as in the classic kernel's verify_correct,
+    // operating on this workgroup's PARTIAL k-range accumulation.
     // (im0, jn0, kbase) place the segment's tile; p_end is the group's end
     // panel within the segment and groups start at multiples of ppg panels:
     // all the fault log needs, and only read in the tripped branch.
     auto verify_correct = [&](int im0, int jn0, int kbase, int p_end, int ppg)
         __attribute__((always_inline)) {
-      float tot = 0.f, chk = 0.f;
-      float cc[FN], cw[FN];
+      float cc[FN], cw[FN], pf[FN];
 #pragma unroll
       for (int fn = 0; fn < FN; ++fn) {
         cc[fn] = cs.cc(fn);
         cw[fn] = cs.cw(fn);
-        chk += cc[fn];
-#pragma unroll
-        for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-          for (int reg = 0; reg < NREG; ++reg) tot += acc[fm][fn][reg];
       }
-      float res = tot - chk;
-#pragma unroll
-      for (int m = 1; m < 64; m <<= 1) res += __shfl_xor(res, m, 64);
+      const float res = detect_partials<FM, FN, MM>(acc, cc, pf);
       if (__builtin_expect(fabsf(res) > tau, 0)) {
         FaultCtx ctx;
         if constexpr (LOG) {
@@ -264,7 +256,7 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
           ctx.k_begin = kbase + ((p_end - 1) / ppg) * ppg * BK;
           ctx.k_end = kbase + p_end * BK;
         }
-        locate_correct<FM, FN, MM, LOG>(acc, cc, cw, sub, tau, ctx);
+        locate_correct<FM, FN, MM, LOG>(acc, cc, cw, pf, sub, tau, ctx);
       }
     };
 

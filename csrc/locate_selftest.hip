@@ -7,7 +7,11 @@
 // the case's fault(s) at arbitrary (fm, fn, reg, lane) sites, and runs both
 // locate_correct and locate_correct_ref, the unscreened sweep-everything
 // form it replaced.  tests/test_gpu_locate_selftest.py asserts the two are
-// bit-identical and that correctable cases restore the clean tile.
+// bit-identical and that correctable cases restore the clean tile.  The
+// shipped function is driven as the fused kernels drive it: the shared
+// detect (detect_partials) runs first and hands it the per-fn partials.  A
+// third entry runs the detect and the screen alone and returns what they
+// computed (tests/test_gpu_detect_shared.py).
 #include <hip/hip_runtime.h>
 
 #include "ft_core.h"
@@ -142,8 +146,11 @@ __global__ __launch_bounds__(64) void locate_selftest_kernel(
       }
   }
 
+  // as the fused kernels do: the detect's partials feed the locate's screen
   fill(true);
-  locate_correct<FM, FN, MM>(tile, cc, cw, sub, tau);
+  float p[FN];
+  (void)detect_partials<FM, FN, MM>(tile, cc, p);
+  locate_correct<FM, FN, MM>(tile, cc, cw, p, sub, tau);
   store(0);
   fill(true);
   locate_correct_ref<FM, FN, MM>(tile, cc, cw, sub, tau);
@@ -214,7 +221,9 @@ __global__ __launch_bounds__(64) void locate_selftest_report_kernel(
   ctx.log.counters = counters + (size_t)cs * FLOG_N_COUNTERS;
   ctx.log.events = events + (size_t)cs * capacity * FLOG_EVENT_DWORDS;
   ctx.log.capacity = capacity;
-  locate_correct<FM, FN, MM, true>(tile, cc, cw, sub, tau, ctx);
+  float p[FN];
+  (void)detect_partials<FM, FN, MM>(tile, cc, p);
+  locate_correct<FM, FN, MM, true>(tile, cc, cw, p, sub, tau, ctx);
   float* o = out + (size_t)cs * E * 64 + lane;
 #pragma unroll
   for (int fm = 0; fm < FM; ++fm)
@@ -223,6 +232,90 @@ __global__ __launch_bounds__(64) void locate_selftest_report_kernel(
 #pragma unroll
       for (int reg = 0; reg < NREG; ++reg)
         o[(size_t)((fm * FN + fn) * NREG + reg) * 64] = tile[fm][fn][reg];
+}
+
+// Detect variant: the shared detect (detect_partials) and the locate's
+// screen (screen_passes) alone, on the same case descriptors and the same
+// tile and checksum construction.  Nothing is corrected.
+// out: [ncases][FM*FN*NREG + 1 + 2*FN][64] floats, lane fastest: the faulty
+//      tile as the detect saw it, then the residual (the same in every lane),
+//      then per fn this lane's partial p[fn], then per fn 1.0 / 0.0 for a
+//      screen that passed / did not (wave-uniform).
+template <int FM, int FN, int MM>
+__global__ __launch_bounds__(64) void detect_selftest_kernel(
+    int ncases, const int* __restrict__ idesc,
+    const float* __restrict__ fdesc, float amp, float* __restrict__ out) {
+  using T = mfma_traits<MM>;
+  constexpr int NREG = T::nreg;
+  constexpr int E = FM * FN * NREG;
+  constexpr int ROWS = E + 1 + 2 * FN;
+  const int cs = blockIdx.x;
+  if (cs >= ncases) return;
+  const int lane = threadIdx.x;
+
+  const int* id = idesc + (size_t)cs * 9;
+  const float* fd = fdesc + (size_t)cs * 3;
+  const int nf = id[0];
+  const float tau = fd[2];
+
+  typename T::acc_t tile[FM][FN];
+  auto fill = [&](bool faulty) __attribute__((always_inline)) {
+#pragma unroll
+    for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+      for (int fn = 0; fn < FN; ++fn)
+#pragma unroll
+        for (int reg = 0; reg < NREG; ++reg) {
+          float v = hash_val(cs, (fm * FN + fn) * NREG + reg, lane, amp);
+          for (int f = 0; f < 2; ++f) {
+            const int* s = id + 1 + 4 * f;
+            if (faulty && f < nf && s[0] == fm && s[1] == fn &&
+                s[2] == reg && s[3] == lane)
+              v += fd[f];
+          }
+          tile[fm][fn][reg] = v;
+        }
+  };
+
+  // same checksum construction as locate_selftest_kernel
+  fill(false);
+  float cc[FN];
+#pragma unroll
+  for (int fn = 0; fn < FN; ++fn) {
+    cc[fn] = 0.f;
+#pragma unroll
+    for (int fm = FM - 1; fm >= 0; --fm)
+#pragma unroll
+      for (int reg = NREG - 1; reg >= 0; --reg) cc[fn] += tile[fm][fn][reg];
+  }
+
+  fill(true);
+  float p[FN];
+  const float res = detect_partials<FM, FN, MM>(tile, cc, p);
+  float* o = out + (size_t)cs * ROWS * 64 + lane;
+#pragma unroll
+  for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+    for (int fn = 0; fn < FN; ++fn)
+#pragma unroll
+      for (int reg = 0; reg < NREG; ++reg)
+        o[(size_t)((fm * FN + fn) * NREG + reg) * 64] = tile[fm][fn][reg];
+  o[(size_t)E * 64] = res;
+#pragma unroll
+  for (int fn = 0; fn < FN; ++fn) {
+    o[(size_t)(E + 1 + fn) * 64] = p[fn];
+    o[(size_t)(E + 1 + FN + fn) * 64] =
+        screen_passes<MM>(p[fn], cc[fn], tau) ? 1.f : 0.f;
+  }
+}
+
+template <int FM, int FN, int MM>
+hipError_t launch_detect_selftest(int ncases, const int* idesc,
+                                  const float* fdesc, float amp, float* out,
+                                  hipStream_t stream) {
+  hipLaunchKernelGGL((detect_selftest_kernel<FM, FN, MM>), dim3(ncases),
+                     dim3(64), 0, stream, ncases, idesc, fdesc, amp, out);
+  return hipGetLastError();
 }
 
 template <int FM, int FN, int MM>
@@ -264,6 +357,23 @@ hipError_t locate_selftest_report_launch(int fm, int fn, int mm, int ncases,
   FT_SELFTEST_REPORT(1, 1, 32)
   FT_SELFTEST_REPORT(1, 1, 16)
 #undef FT_SELFTEST_REPORT
+  return hipErrorInvalidValue;
+}
+
+hipError_t detect_selftest_launch(int fm, int fn, int mm, int ncases,
+                                  const int* idesc, const float* fdesc,
+                                  float amp, float* out, hipStream_t stream) {
+  if (ncases < 1) return hipErrorInvalidValue;
+#define FT_SELFTEST_DETECT(FM_, FN_, MM_)                                   \
+  if (fm == FM_ && fn == FN_ && mm == MM_)                                  \
+    return launch_detect_selftest<FM_, FN_, MM_>(ncases, idesc, fdesc, amp, \
+                                                 out, stream);
+  FT_SELFTEST_DETECT(4, 2, 32)
+  FT_SELFTEST_DETECT(2, 1, 32)
+  FT_SELFTEST_DETECT(1, 2, 32)
+  FT_SELFTEST_DETECT(1, 1, 32)
+  FT_SELFTEST_DETECT(1, 1, 16)
+#undef FT_SELFTEST_DETECT
   return hipErrorInvalidValue;
 }
 

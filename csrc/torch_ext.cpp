@@ -161,6 +161,38 @@ at::Tensor locate_selftest(int64_t fm, int64_t fn, int64_t mm,
   return out;
 }
 
+// Detect variant: (ncases, fm*fn*nreg + 1 + 2*fn, 64) — the faulty tile, the
+// wave residual, per fn the lane partial p[fn], per fn the screen's verdict.
+at::Tensor detect_selftest(int64_t fm, int64_t fn, int64_t mm,
+                           at::Tensor idesc, at::Tensor fdesc, double amp) {
+  TORCH_CHECK(idesc.is_cuda() && fdesc.is_cuda(),
+              "detect_selftest: descriptors must be on a GPU device");
+  TORCH_CHECK(idesc.scalar_type() == at::kInt && idesc.is_contiguous() &&
+                  idesc.dim() == 2 && idesc.size(1) == 9,
+              "detect_selftest: idesc must be contiguous int32 (ncases, 9)");
+  const int64_t ncases = idesc.size(0);
+  TORCH_CHECK(fdesc.scalar_type() == at::kFloat && fdesc.is_contiguous() &&
+                  fdesc.dim() == 2 && fdesc.size(0) == ncases &&
+                  fdesc.size(1) == 3,
+              "detect_selftest: fdesc must be contiguous fp32 (ncases, 3)");
+  TORCH_CHECK(ncases >= 1 && ncases <= (1 << 20),
+              "detect_selftest: 1..2^20 cases");
+  TORCH_CHECK(fm >= 1 && fm <= 4 && fn >= 1 && fn <= 2 &&
+                  (mm == 32 || mm == 16),
+              "detect_selftest: unsupported (fm, fn, mm)");
+  const int64_t nreg = mm == 32 ? 16 : 4;
+  at::Tensor out = at::empty({ncases, fm * fn * nreg + 1 + 2 * fn, 64},
+                             fdesc.options());
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipError_t err = ftsgemm::detect_selftest_launch(
+      (int)fm, (int)fn, (int)mm, (int)ncases, idesc.const_data_ptr<int>(),
+      fdesc.const_data_ptr<float>(), (float)amp,
+      out.mutable_data_ptr<float>(), stream.stream());
+  TORCH_CHECK(err == hipSuccess, "detect_selftest: unsupported (fm, fn, mm) ",
+              "or launch failure: ", hipGetErrorString(err));
+  return out;
+}
+
 // Report variant: (corrected tiles (ncases, fm*fn*nreg, 64), counters
 // (ncases, 5) int32, events (ncases, capacity, 8) int32), one log per case.
 std::tuple<at::Tensor, at::Tensor, at::Tensor> locate_selftest_report(
@@ -213,6 +245,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("tier_supported", &tier_supported, "tile divisibility check");
   m.def("locate_selftest", &locate_selftest,
         "device self-test of the ABFT locate/correct");
+  m.def("detect_selftest", &detect_selftest,
+        "device self-test of the shared ABFT detect and the locate's screen");
   m.def("locate_selftest_report", &locate_selftest_report,
         "self-test of the shipped locate/correct with a fault log per case");
 }

@@ -112,6 +112,19 @@ def locate_selftest(fm: int, fn: int, mm: int, idesc: torch.Tensor,
     return _require_ext().locate_selftest(fm, fn, mm, idesc, fdesc, amp)
 
 
+def detect_selftest(fm: int, fn: int, mm: int, idesc: torch.Tensor,
+                    fdesc: torch.Tensor, amp: float) -> torch.Tensor:
+    """locate_selftest's detect twin: runs only the fused kernels' shared
+    detect and the locate's fp32 screen on the same descriptors and the same
+    synthetic tile.  Returns (ncases, fm*fn*nreg + 1 + 2*fn, 64), lane last:
+    rows [0, fm*fn*nreg) the faulty tile (element (fm*FN + fn)*nreg + reg),
+    then the wave residual the detect compares with tau (the same in all 64
+    lanes), then per fn the lane's partial sum p[fn] over fm and reg, then
+    per fn 1.0 where the screen passed the fragment column and 0.0 where it
+    did not."""
+    return _require_ext().detect_selftest(fm, fn, mm, idesc, fdesc, amp)
+
+
 def choose_tier(m: int, n: int, k: int):
     """Pick the fastest applicable tier for a problem shape, or None when no
     hand-tiled tier divides the shape (callers fall back to rocBLAS).
