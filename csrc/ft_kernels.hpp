@@ -253,7 +253,7 @@ __device__ __attribute__((always_inline)) inline bool screen_passes(
 
 // ABFT ratio locate + in-register correct of one wave tile, shared by the
 // classic and the stream-K kernel (entered only after the cheap detect in
-// their verify_correct tripped; the scheme itself is described there).
+// verify_window tripped; the scheme itself is described in sgemm_mfma).
 // acc[FM][FN] is the wave's accumulator tile, cc/cw this lane's plain and
 // row-weighted column-checksum partials, p the per-fn partial sums the
 // detect (detect_partials) just formed of the same acc, sub = lane / MM.
@@ -423,37 +423,180 @@ __global__ __launch_bounds__(256) void segsum_kernel(
   }
 }
 
-template <int BM, int BN, int BK, int WM, int WN, int MM, bool ABFT,
-          bool INJECT, int OCC = 2, bool LOG = false>
-__global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
-    int M, int N, int K, const float* __restrict__ A,
-    const float* __restrict__ B, float* __restrict__ C, float alpha,
-    float beta, int verify_iters, int inject_stride, float tau, float inj_mag,
-    const float* __restrict__ SA, int sstr, FaultLog flog) {
-  using T = mfma_traits<MM>;
-  constexpr int KSTEP = T::kstep;
-  constexpr int NREG = T::nreg;
-  constexpr int WAVES_M = BM / WM, WAVES_N = BN / WN;
-  constexpr int NWAVES = WAVES_M * WAVES_N;
-  constexpr int THREADS = NWAVES * 64;
-  constexpr int FM = WM / MM, FN = WN / MM;
-  constexpr int BUF = (BM + BN) * BK;  // floats per double-buffer half
+// ---------------------------------------------------------------------------
+// Device building blocks shared by the classic kernel (sgemm_mfma, below),
+// the stream-K kernel and its fixup pass (ft_streamk.hpp).  All are inlined
+// into their callers; the kernels keep only their own work decomposition.
+// ---------------------------------------------------------------------------
+
+// Where one thread sits in its workgroup's tile: wave and lane, the lane's
+// k-slice within one MFMA k-step (sub) and its row of the A fragment / column
+// of the B fragment (r), and the wave tile's offset (wi0, wj0) in the block
+// tile.
+struct thread_pos {
+  int tid, wave, lane, sub, r, wm_idx, wi0, wj0;
+};
+
+// Compile-time geometry of one tile configuration: thread layout, fragment
+// counts and the LDS map.
+template <int BM_, int BN_, int BK_, int WM_, int WN_, int MM_, bool ABFT>
+struct tile_geom {
+  using T = mfma_traits<MM_>;
+  static constexpr int BM = BM_, BN = BN_, BK = BK_;
+  static constexpr int WM = WM_, WN = WN_, MM = MM_;
+  static constexpr int KSTEP = T::kstep;
+  static constexpr int NREG = T::nreg;
+  static constexpr int WAVES_M = BM / WM, WAVES_N = BN / WN;
+  static constexpr int NWAVES = WAVES_M * WAVES_N;
+  static constexpr int THREADS = NWAVES * 64;
+  static constexpr int FM = WM / MM, FN = WN / MM;
+  static constexpr int TPT = FM * FN * NREG;  // per-thread floats of one tile
+  static constexpr int BUF = (BM + BN) * BK;  // floats per double-buffer half
   // ABFT checksum strips: per wave, a private [2 pair-buffers][sa(64) |
   // saw(64)] window of the precomputed segment sums, streamed by
   // global_load_lds.  Only A-side sums are needed: the column checksums
   // detect, the weighted ones locate the row, and the column is lane-local.
-  constexpr int STRIP_OFF = 2 * BUF;
-  constexpr int LDS_FLOATS = ABFT ? (STRIP_OFF + NWAVES * 256) : (2 * BUF);
+  static constexpr int STRIP_OFF = 2 * BUF;
+  static constexpr int LDS_FLOATS =
+      ABFT ? (STRIP_OFF + NWAVES * 256) : (2 * BUF);
+  // A strip load covers 64 k values = PPS panels (one stream-K work unit);
+  // strips are double buffered by strip-window parity.
+  static constexpr int PPS = 64 / BK;
+  static_assert(!ABFT || (BK <= 64 && 64 % BK == 0),
+                "ABFT needs BK dividing 64");
 
-  __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
+  static __device__ inline thread_pos thread(int tid) {
+    const int wave = tid >> 6, lane = tid & 63;
+    const int wm_idx = wave / WAVES_N, wn_idx = wave % WAVES_N;
+    return {tid, wave, lane, lane / MM, lane % MM, wm_idx, wm_idx * WM,
+            wn_idx * WN};
+  }
+  // this wave's strip buffer for 64-k windows of parity pb
+  static __device__ inline float* strip(float* lds, int wave, int pb) {
+    return &lds[STRIP_OFF + wave * 256 + pb * 128];
+  }
+};
 
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63;
-  const int sub = lane / MM;  // k-slice within one MFMA k-step
-  const int r = lane % MM;    // row index of A fragment / col index of B
-  const int wm_idx = wave / WAVES_N, wn_idx = wave % WAVES_N;
-  const int wi0 = wm_idx * WM;
-  const int wj0 = wn_idx * WN;
+// async HBM -> LDS copy of BYTES per lane.  The source address is PER-LANE;
+// the LDS side is a wave-uniform base + lane * BYTES.
+template <int BYTES>
+__device__ __attribute__((always_inline)) inline void glds(const float* src,
+                                                           float* dst) {
+  const auto* s = (const __attribute__((address_space(1))) void*)src;
+  auto* d = (__attribute__((address_space(3))) void*)dst;
+  // the builtin takes its size as a literal only
+  static_assert(BYTES == 16 || BYTES == 4);
+  if constexpr (BYTES == 16)
+    __builtin_amdgcn_global_load_lds(s, d, 16, 0, 0);
+  else
+    __builtin_amdgcn_global_load_lds(s, d, 4, 0, 0);
+}
+
+// Stages one ROWS x BK operand panel (rows row0.. of the column-major
+// matrix g with leading dimension ld, columns k0..) into dst, LDS layout
+// [k][row] with row contiguous, 16 B per lane.  Staging passes may be
+// fractional in WHOLE WAVES (e.g. the fused tall twin at BKF=8 stages a
+// 256-float B panel with a 128-thread block: 0 full passes + a 64-lane
+// remainder by wave 0).
+template <int ROWS, int BK, int THREADS>
+__device__ __attribute__((always_inline)) inline void stage_operand(
+    float* dst, const float* __restrict__ g, int ld, int row0, int k0, int tid,
+    int wave) {
+  constexpr int GF = (ROWS * BK) / (THREADS * 4);  // full dwordx4 passes
+  constexpr int GR = (ROWS * BK / 4) % THREADS;    // remainder lanes
+  static_assert(GR % 64 == 0, "stage remainder must be whole waves");
+  static_assert(GF + GR > 0, "tile too small");
+  auto pass = [&](int c0) __attribute__((always_inline)) {
+    const int f = (c0 + tid) * 4;  // per-lane float index
+    const int k = f / ROWS, i = f % ROWS;
+    glds<16>(g + (row0 + i) + (size_t)(k0 + k) * ld,
+             dst + (c0 + wave * 64) * 4);
+  };
+#pragma unroll
+  for (int t = 0; t < GF; ++t) pass(t * THREADS);
+  if constexpr (GR > 0) {
+    if (tid < GR) pass(GF * THREADS);
+  }
+}
+
+// ABFT strip staging: one 4-B/lane glds pair per TWO K panels.  Each wave
+// streams its own 64-k window of the precomputed segment sums into its
+// private LDS strip dst.  No extra barrier, no cooperative pass: the strips
+// ride the same prefetch pipeline as the A/B panels and are drained by the
+// same end-of-panel __syncthreads.
+// Workspace layout (set up by the launcher): per WM-row band of A (segA),
+// one row of 2*sstr floats with (plain, row-weighted) segment sums
+// INTERLEAVED at [2k], [2k+1] — a 64-k window is 128 contiguous floats,
+// fetched by two 64-lane glds loads (lane l fetches pair-element 2*k0 + l)
+// and consumed with one ds_read_b64 per k-step.
+__device__ __attribute__((always_inline)) inline void strip_stage(
+    float* dst, const float* __restrict__ SA, int sstr, int segA, int k0,
+    int lane) {
+  const float* ga = SA + (size_t)segA * 2 * sstr + 2 * k0 + lane;
+  glds<4>(ga, dst);
+  glds<4>(ga + 64, dst + 64);
+}
+
+// ABFT verify / locate / correct of one wave tile: wave-autonomous,
+// registers only.  Two-phase: the cheap detect (detect_partials: total tile
+// sum vs total checksum) runs every verify window.  Its residual is
+// identical across the wave's lanes, so the branch is uniform, and only a
+// wave that actually absorbed a fault enters locate_correct(), which gets
+// the detect's per-fn partials: the fault-free common case never pays for
+// location.
+//
+// (i0_tile, j0_tile) is the block tile's first row / column and kbase its
+// first k (0 in the classic kernel, the segment's start in stream-K); p_end
+// is the window's end panel counted from kbase, and windows start at
+// multiples of ppg panels.  These only feed the fault-log context, which is
+// built in the cold branch: the window's first panel needs no register of
+// its own in the loop.
+template <class G, bool LOG>
+__device__ __attribute__((always_inline)) inline void verify_window(
+    typename G::T::acc_t (&acc)[G::FM][G::FN], const checksum_regs<G::FN>& cs,
+    int sub, float tau, const FaultLog& flog, int i0_tile, int j0_tile,
+    int kbase, int p_end, int ppg) {
+  constexpr int FM = G::FM, FN = G::FN, MM = G::MM;
+  float cc[FN], cw[FN], p[FN];
+#pragma unroll
+  for (int fn = 0; fn < FN; ++fn) {
+    cc[fn] = cs.cc(fn);
+    cw[fn] = cs.cw(fn);
+  }
+  const float res = detect_partials<FM, FN, MM>(acc, cc, p);
+  if (__builtin_expect(fabsf(res) > tau, 0)) {
+    FaultCtx ctx;
+    if constexpr (LOG) {
+      ctx.log = flog;
+      const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+      ctx.i0 = i0_tile + (wv / G::WAVES_N) * G::WM;
+      ctx.j0 = j0_tile + (wv % G::WAVES_N) * G::WN;
+      ctx.k_begin = kbase + ((p_end - 1) / ppg) * ppg * G::BK;
+      ctx.k_end = kbase + p_end * G::BK;
+    }
+    locate_correct<FM, FN, MM, LOG>(acc, cc, cw, p, sub, tau, ctx);
+  }
+}
+
+template <int BM, int BN, int BK, int WM, int WN, int MM, bool ABFT,
+          bool INJECT, int OCC = 2, bool LOG = false>
+__global__ __launch_bounds__(
+    (tile_geom<BM, BN, BK, WM, WN, MM, ABFT>::THREADS), OCC) void sgemm_mfma(
+    int M, int N, int K, const float* __restrict__ A,
+    const float* __restrict__ B, float* __restrict__ C, float alpha,
+    float beta, int verify_iters, int inject_stride, float tau, float inj_mag,
+    const float* __restrict__ SA, int sstr, FaultLog flog) {
+  using G = tile_geom<BM, BN, BK, WM, WN, MM, ABFT>;
+  using T = typename G::T;
+  constexpr int KSTEP = G::KSTEP, THREADS = G::THREADS, FM = G::FM,
+                FN = G::FN, BUF = G::BUF, STRIP_OFF = G::STRIP_OFF,
+                PPS = G::PPS;
+
+  __shared__ __attribute__((aligned(16))) float lds[G::LDS_FLOATS];
+
+  const thread_pos t = G::thread(threadIdx.x);
+  const int tid = t.tid, wave = t.wave, lane = t.lane, sub = t.sub, r = t.r,
+            wm_idx = t.wm_idx, wi0 = t.wi0, wj0 = t.wj0;
   const int bx = blockIdx.x, by = blockIdx.y;
   const int im0 = bx * BM;
   const int jn0 = by * BN;
@@ -462,107 +605,18 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
   checksum_regs<FN> cs;  // running column checksums of this wave's tile
   cs.clear();
 
-  // ---- async HBM -> LDS staging (global_load_lds, 16 B per lane) ----
-  // staging passes may be fractional in WHOLE WAVES (e.g. the fused tall
-  // twin at BKF=8 stages a 256-float B panel with a 128-thread block:
-  // GB=0 full passes + a 64-lane remainder by wave 0)
-  constexpr int GA = (BM * BK) / (THREADS * 4);  // dwordx4 chunks for A
-  constexpr int GAR = (BM * BK / 4) % THREADS;   // remainder lanes
-  constexpr int GB = (BN * BK) / (THREADS * 4);
-  constexpr int GBR = (BN * BK / 4) % THREADS;
-  static_assert(GAR % 64 == 0 && GBR % 64 == 0,
-                "stage remainder must be whole waves");
-  static_assert(GA + GAR > 0 && GB + GBR > 0, "tile too small");
-
   auto stage = [&](int q, int k0) __attribute__((always_inline)) {
-    float* dstA = &lds[q * BUF];
-    float* dstB = &lds[q * BUF + BM * BK];
-#pragma unroll
-    for (int t = 0; t < GA; ++t) {
-      const int f = (t * THREADS + tid) * 4;  // per-lane float index
-      const int k = f / BM, i = f % BM;       // LDS layout [k][i], i contig
-      const float* g = A + (im0 + i) + (size_t)(k0 + k) * M;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)g,
-          (__attribute__((address_space(3))) void*)(dstA +
-                                                    (t * THREADS + wave * 64) *
-                                                        4),
-          16, 0, 0);
-    }
-    if constexpr (GAR > 0) {
-      if (tid < GAR) {
-        const int f = (GA * THREADS + tid) * 4;
-        const int k = f / BM, i = f % BM;
-        const float* g = A + (im0 + i) + (size_t)(k0 + k) * M;
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)g,
-            (__attribute__((address_space(3))) void*)(dstA +
-                                                      (GA * THREADS +
-                                                       wave * 64) *
-                                                          4),
-            16, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < GB; ++t) {
-      const int f = (t * THREADS + tid) * 4;
-      const int k = f / BN, j = f % BN;
-      const float* g = B + (jn0 + j) + (size_t)(k0 + k) * N;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)g,
-          (__attribute__((address_space(3))) void*)(dstB +
-                                                    (t * THREADS + wave * 64) *
-                                                        4),
-          16, 0, 0);
-    }
-    if constexpr (GBR > 0) {
-      if (tid < GBR) {
-        const int f = (GB * THREADS + tid) * 4;
-        const int k = f / BN, j = f % BN;
-        const float* g = B + (jn0 + j) + (size_t)(k0 + k) * N;
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) void*)g,
-            (__attribute__((address_space(3))) void*)(dstB +
-                                                      (GB * THREADS +
-                                                       wave * 64) *
-                                                          4),
-            16, 0, 0);
-      }
-    }
+    stage_operand<BM, BK, THREADS>(&lds[q * BUF], A, M, im0, k0, tid, wave);
+    stage_operand<BN, BK, THREADS>(&lds[q * BUF + BM * BK], B, N, jn0, k0, tid,
+                                   wave);
   };
 
-  // ---- ABFT strip staging: one 4-B/lane glds pair per TWO K panels ----
-  // Each wave streams its own 64-k window of the precomputed segment sums
-  // into a private LDS strip.  No extra barrier, no cooperative pass: the
-  // strips ride the same prefetch pipeline as the A/B panels and are
-  // drained by the same end-of-panel __syncthreads.
-  // Workspace layout (set up by the launcher): per WM-row band of A, one
-  // row of 2*sstr floats with (plain, row-weighted) segment sums
-  // INTERLEAVED at [2k], [2k+1] — a 64-k window is 128 contiguous floats,
-  // fetched by two 64-lane glds loads and consumed with one ds_read_b64
-  // per k-step.
-  const int segA = bx * WAVES_M + wm_idx;
-  auto strip_stage = [&](int pb, int k0) __attribute__((always_inline)) {
-    // glds source addresses are PER-LANE (the LDS side is uniform base +
-    // lane*size): lane l fetches pair-element (2*k0 + l).
-    const float* ga = SA + (size_t)segA * 2 * sstr + 2 * k0 + lane;
-    float* dst = &lds[STRIP_OFF + wave * 256 + pb * 128];
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)ga,
-        (__attribute__((address_space(3))) void*)dst, 4, 0, 0);
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)(ga + 64),
-        (__attribute__((address_space(3))) void*)(dst + 64), 4, 0, 0);
+  const int segA = bx * G::WAVES_M + wm_idx;  // this wave's WM-row band of A
+  auto stage_strip = [&](int pb, int k0) __attribute__((always_inline)) {
+    strip_stage(G::strip(lds, wave, pb), SA, sstr, segA, k0, lane);
   };
 
-  // ---- ABFT verify / locate / correct: wave-autonomous, registers only ----
-  // Two-phase: a cheap detect (compare the total tile sum against the total
-  // checksum — FM*FN*NREG adds + a butterfly) runs every verify window;
-  // locate_correct() (above, shared with the stream-K kernel) is entered
-  // only when the residual trips the threshold (i.e. in
-  // the wave that actually absorbed a fault), so the fault-free common case
-  // never pays for location.
-  //
+  // ---- ABFT scheme (verify_window -> locate_correct, above) ----
   // Ratio locate: the fault's COLUMN is lane-local (acc column == lane's
   // r), its magnitude is the column residual rc; its ROW index is
   // round(rw / rc) where rw is the residual of the row-index-WEIGHTED
@@ -582,33 +636,10 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
   // fragment's row range nothing matches and the kernel fail-safes to
   // detected-but-uncorrected.  Faults in different columns (the common
   // double-fault shape) locate independently per lane and correct fine.
-  auto verify_correct = [&](int it_end) __attribute__((always_inline)) {
-    // Cheap detect (detect_partials, above): total tile sum vs total
-    // checksum.  The residual is identical across the wave's lanes, so
-    // the branch is uniform; only a wave that actually absorbed a fault
-    // enters locate_correct(), which gets the detect's per-fn partials.
-    float cc[FN], cw[FN], p[FN];
-#pragma unroll
-    for (int fn = 0; fn < FN; ++fn) {
-      cc[fn] = cs.cc(fn);
-      cw[fn] = cs.cw(fn);
-    }
-    const float res = detect_partials<FM, FN, MM>(acc, cc, p);
-    if (__builtin_expect(fabsf(res) > tau, 0)) {
-      // Fault-log context, built here in the cold branch only.  it_end is
-      // the burst's end panel and bursts start at multiples of verify_iters,
-      // so the burst's first panel needs no register of its own in the loop.
-      FaultCtx ctx;
-      if constexpr (LOG) {
-        ctx.log = flog;
-        const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        ctx.i0 = im0 + (wv / WAVES_N) * WM;
-        ctx.j0 = jn0 + (wv % WAVES_N) * WN;
-        ctx.k_begin = ((it_end - 1) / verify_iters) * verify_iters * BK;
-        ctx.k_end = it_end * BK;
-      }
-      locate_correct<FM, FN, MM, LOG>(acc, cc, cw, p, sub, tau, ctx);
-    }
+  // Bursts start at multiples of verify_iters panels, from k = 0.
+  auto verify = [&](int it_end) __attribute__((always_inline)) {
+    verify_window<G, LOG>(acc, cs, sub, tau, flog, im0, jn0, 0, it_end,
+                          verify_iters);
   };
 
   // ---- main K loop: one barrier per BK panel, glds prefetch overlaps ----
@@ -617,12 +648,8 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
   // run at burst boundaries only (a conditional VALU read of acc inside the
   // panel loop makes hipcc shuttle the whole accumulator file through VGPR
   // copies every panel — measured 2x wall time on the huge tier).
-  // A strip load covers 64 k values = PPS panels; strips are double
-  // buffered by strip-window parity.
-  constexpr int PPS = 64 / BK;  // panels per strip window (BK <= 64)
-  static_assert(64 % BK == 0 || !ABFT, "ABFT needs BK dividing 64");
   stage(0, 0);
-  if constexpr (ABFT) strip_stage(0, 0);  // window (panels 0..PPS-1)
+  if constexpr (ABFT) stage_strip(0, 0);  // window 0 (panels 0..PPS-1)
   FT_PARA_SYNC();
   __syncthreads();  // drains in-flight glds
 
@@ -644,8 +671,8 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
         stage(q ^ 1, (it + 1) * BK);
         // a new strip window rides along every PPS-th panel prefetch
         if constexpr (ABFT) {
-          if ((it + 1) % PPS == 0) strip_stage(((it + 1) / PPS) & 1,
-                                               (it + 1) * BK);
+          if ((it + 1) % PPS == 0)
+            stage_strip(((it + 1) / PPS) & 1, (it + 1) * BK);
         }
       }
       FT_PARA_SYNC();
@@ -670,6 +697,9 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
       // the pairs, ordered after the barrier, is what pins it
       // (docs/ABLATION.md §5b).  Per lane the fmas into each checksum
       // still run in ascending k: bit-identical.
+      // This panel body and the alpha/beta epilogue below are written out
+      // again in ft_streamk.hpp: as shared functions they changed register
+      // counts or the epilogue's rounding (docs/ABLATION.md §5e).
       constexpr int NKK = BK / KSTEP;
       constexpr bool DEFER = ABFT && defer_encode<FM, FN>;
       f32x2 swv[DEFER ? NKK : 1];
@@ -709,7 +739,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
         for (int kk = 0; kk < NKK; ++kk) cs.encode(swv[kk], bv[kk]);
       }
     }
-    if constexpr (ABFT) verify_correct(it);
+    if constexpr (ABFT) verify(it);
   }
 
   // ---- epilogue: alpha/beta merge, float4 along column-major columns ----
@@ -720,7 +750,7 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC) void sgemm_mfma(
       const int j = jn0 + wj0 + fn * MM + r;
       float* colbase = C + (size_t)j * M + im0 + wi0 + fm * MM;
 #pragma unroll
-      for (int g = 0; g < NREG / 4; ++g) {
+      for (int g = 0; g < G::NREG / 4; ++g) {
         float* p = colbase + 4 * sub + 8 * g;
         f32x4 out;
         if (beta != 0.f) {

@@ -58,54 +58,75 @@ __device__ inline int sk_wg_of_unit(int u, int q, int rem) {
                              : rem + (u - rem * (q + 1)) / q;
 }
 
+// Split-tile partial slots: slot s is BM*BN floats, thread t's TPT
+// accumulator values at [t * TPT], in (fm, fn, reg) order.  The main kernel
+// writes this layout and the fixup kernel reads it back.
+template <class G, class F>
+__device__ inline F* partial_slot(F* partials, int s, int tid) {
+  return partials + (size_t)s * (G::BM * G::BN) + tid * G::TPT;
+}
+
+template <class G>
+__device__ __attribute__((always_inline)) inline void store_partial(
+    float* slot, const typename G::T::acc_t (&acc)[G::FM][G::FN]) {
+#pragma unroll
+  for (int fm = 0; fm < G::FM; ++fm)
+#pragma unroll
+    for (int fn = 0; fn < G::FN; ++fn)
+#pragma unroll
+      for (int g4 = 0; g4 < G::NREG / 4; ++g4) {
+        f32x4 v;
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) v[q4] = acc[fm][fn][4 * g4 + q4];
+        *(f32x4*)(slot + (fm * G::FN + fn) * G::NREG + 4 * g4) = v;
+      }
+}
+
+// s = slot (ADD false) or s += slot (ADD true), element e of s being
+// accumulator register e % NREG of fragment e / NREG
+template <class G, bool ADD>
+__device__ __attribute__((always_inline)) inline void load_partial(
+    float (&s)[G::TPT], const float* slot) {
+#pragma unroll
+  for (int e4 = 0; e4 < G::TPT; e4 += 4) {
+    const f32x4 v = *(const f32x4*)(slot + e4);
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4)
+      s[e4 + q4] = ADD ? s[e4 + q4] + v[q4] : v[q4];
+  }
+}
+
 // Split-tile combine pass: one workgroup per output tile, with the SAME
 // thread geometry as the main kernel so thread t reads back exactly the
 // fragment elements thread t of each contributor wrote.  Fully-owned
 // tiles exit immediately (the main kernel already wrote them).
 template <int BM, int BN, int WM, int WN, int MM>
-static __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN))
-void sk_fixup_kernel(int M, int N, int upt, int G, float alpha, float beta,
+static __global__ __launch_bounds__(
+    (tile_geom<BM, BN, 64, WM, WN, MM, false>::THREADS))
+void sk_fixup_kernel(int M, int N, int upt, int nwg, float alpha, float beta,
                      float* __restrict__ C,
                      const float* __restrict__ partials) {
-  using T = mfma_traits<MM>;
-  constexpr int NREG = T::nreg;
-  constexpr int WAVES_N = BN / WN;
-  constexpr int FM = WM / MM, FN = WN / MM;
-  constexpr int TPT = FM * FN * NREG;
+  // BK plays no part in the thread geometry or the slot layout
+  using G = tile_geom<BM, BN, 64, WM, WN, MM, false>;
   const int tile = blockIdx.x;
   const int ntm = M / BM;
   const int total = ntm * (N / BN) * upt;
-  const int q = total / G, rem = total % G;
+  const int q = total / nwg, rem = total % nwg;
   const int g0 = sk_wg_of_unit(tile * upt, q, rem);
   const int gl = sk_wg_of_unit(tile * upt + upt - 1, q, rem);
   if (g0 == gl) return;  // fully owned -> already epilogued
 
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63;
-  const int sub = lane / MM;
-  const int r = lane % MM;
-  const int wm_idx = wave / WAVES_N, wn_idx = wave % WAVES_N;
-  const int wi0 = wm_idx * WM;
-  const int wj0 = wn_idx * WN;
+  constexpr int FM = G::FM, FN = G::FN, NREG = G::NREG;
+  const thread_pos t = G::thread(threadIdx.x);
+  const int sub = t.sub, r = t.r, wi0 = t.wi0, wj0 = t.wj0;
   const int bx = tile % ntm, by = tile / ntm;
   const int im0 = bx * BM, jn0 = by * BN;
 
-  float s[TPT];
-  {  // g0's tail partial (slot 2*g0+1), then every head partial in (g0,gl]
-    const float* slot = partials + (size_t)(2 * g0 + 1) * (BM * BN) +
-                        tid * TPT;
-#pragma unroll
-    for (int e = 0; e < TPT; ++e) s[e] = slot[e];
-  }
-  for (int gc = g0 + 1; gc <= gl; ++gc) {
-    const float* slot = partials + (size_t)(2 * gc) * (BM * BN) + tid * TPT;
-#pragma unroll
-    for (int e4 = 0; e4 < TPT; e4 += 4) {
-      const f32x4 v = *(const f32x4*)(slot + e4);
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) s[e4 + q4] += v[q4];
-    }
-  }
+  // g0's tail partial (slot 2*g0+1), then every head partial in (g0,gl]
+  float s[G::TPT];
+  load_partial<G, false>(s, partial_slot<G>(partials, 2 * g0 + 1, t.tid));
+  for (int gc = g0 + 1; gc <= gl; ++gc)
+    load_partial<G, true>(s, partial_slot<G>(partials, 2 * gc, t.tid));
 #pragma unroll
   for (int fm = 0; fm < FM; ++fm)
 #pragma unroll
@@ -133,96 +154,51 @@ void sk_fixup_kernel(int M, int N, int upt, int G, float alpha, float beta,
 
 template <int BM, int BN, int BK, int WM, int WN, int MM, bool ABFT,
           bool INJECT, int OCC = 2, bool LOG = false>
-__global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), OCC)
+__global__ __launch_bounds__(
+    (tile_geom<BM, BN, BK, WM, WN, MM, ABFT>::THREADS), OCC)
 void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
                         const float* __restrict__ B, float* __restrict__ C,
                         float alpha, float beta, int istride, float tau,
                         float inj_mag, const float* __restrict__ SA, int sstr,
                         float* __restrict__ partials, FaultLog flog) {
-  using T = mfma_traits<MM>;
-  constexpr int KSTEP = T::kstep;
-  constexpr int NREG = T::nreg;
-  constexpr int WAVES_M = BM / WM, WAVES_N = BN / WN;
-  constexpr int NWAVES = WAVES_M * WAVES_N;
-  constexpr int THREADS = NWAVES * 64;
-  constexpr int FM = WM / MM, FN = WN / MM;
-  constexpr int BUF = (BM + BN) * BK;
-  constexpr int PPS = 64 / BK;  // panels per strip window / work unit
+  using G = tile_geom<BM, BN, BK, WM, WN, MM, ABFT>;
+  using T = typename G::T;
+  constexpr int KSTEP = G::KSTEP, THREADS = G::THREADS, FM = G::FM,
+                FN = G::FN, BUF = G::BUF, STRIP_OFF = G::STRIP_OFF,
+                PPS = G::PPS;  // PPS panels = one 64-k work unit
   static_assert(64 % BK == 0 && BK <= 64, "stream-K unit is 64 k");
-  constexpr int STRIP_OFF = 2 * BUF;
-  constexpr int LDS_FLOATS = ABFT ? (STRIP_OFF + NWAVES * 256) : (2 * BUF);
 
-  __shared__ __attribute__((aligned(16))) float lds[LDS_FLOATS];
+  __shared__ __attribute__((aligned(16))) float lds[G::LDS_FLOATS];
 
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63;
-  const int sub = lane / MM;
-  const int r = lane % MM;
-  const int wm_idx = wave / WAVES_N, wn_idx = wave % WAVES_N;
-  const int wi0 = wm_idx * WM;
-  const int wj0 = wn_idx * WN;
+  const thread_pos t = G::thread(threadIdx.x);
+  const int tid = t.tid, wave = t.wave, lane = t.lane, sub = t.sub, r = t.r,
+            wm_idx = t.wm_idx, wi0 = t.wi0, wj0 = t.wj0;
 
   const int ntm = M / BM;
   const int upt = K >> 6;  // units (64-k windows) per tile
   const int total = ntm * (N / BN) * upt;
-  // balanced contiguous unit ranges: first (total % G) workgroups take one
-  // extra unit
+  // balanced contiguous unit ranges: the first (total % gridDim.x)
+  // workgroups take one extra unit
   const int g = blockIdx.x;
   const int q = total / gridDim.x, rem = total % gridDim.x;
   int u = g * q + (g < rem ? g : rem);
   const int u_end = u + q + (g < rem ? 1 : 0);
 
-  constexpr int GA = (BM * BK) / (THREADS * 4);
-  constexpr int GB = (BN * BK) / (THREADS * 4);
-  static_assert(GA >= 1 && GB >= 1, "tile too small for this thread count");
-
   auto stage = [&](int qb, int k0, int im0, int jn0)
       __attribute__((always_inline)) {
-    float* dstA = &lds[qb * BUF];
-    float* dstB = &lds[qb * BUF + BM * BK];
-#pragma unroll
-    for (int t = 0; t < GA; ++t) {
-      const int f = (t * THREADS + tid) * 4;
-      const int k = f / BM, i = f % BM;
-      const float* gp = A + (im0 + i) + (size_t)(k0 + k) * M;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)gp,
-          (__attribute__((address_space(3))) void*)(dstA +
-                                                    (t * THREADS + wave * 64) *
-                                                        4),
-          16, 0, 0);
-    }
-#pragma unroll
-    for (int t = 0; t < GB; ++t) {
-      const int f = (t * THREADS + tid) * 4;
-      const int k = f / BN, j = f % BN;
-      const float* gp = B + (jn0 + j) + (size_t)(k0 + k) * N;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)gp,
-          (__attribute__((address_space(3))) void*)(dstB +
-                                                    (t * THREADS + wave * 64) *
-                                                        4),
-          16, 0, 0);
-    }
+    stage_operand<BM, BK, THREADS>(&lds[qb * BUF], A, M, im0, k0, tid, wave);
+    stage_operand<BN, BK, THREADS>(&lds[qb * BUF + BM * BK], B, N, jn0, k0,
+                                   tid, wave);
   };
-
-  // interleaved (plain, weighted) segment-sum pairs: see ft_kernels.hpp
-  auto strip_stage = [&](int pb, int k0, int segA)
+  auto stage_strip = [&](int pb, int k0, int segA)
       __attribute__((always_inline)) {
-    const float* ga = SA + (size_t)segA * 2 * sstr + 2 * k0 + lane;
-    float* dst = &lds[STRIP_OFF + wave * 256 + pb * 128];
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)ga,
-        (__attribute__((address_space(3))) void*)dst, 4, 0, 0);
-    __builtin_amdgcn_global_load_lds(
-        (const __attribute__((address_space(1))) void*)(ga + 64),
-        (__attribute__((address_space(3))) void*)(dst + 64), 4, 0, 0);
+    strip_stage(G::strip(lds, wave, pb), SA, sstr, segA, k0, lane);
   };
 
-  // Accumulators and the ABFT verify machinery are declared ONCE, outside
-  // the tile loop, and re-zeroed per segment — declaring them inside the
-  // loop body made the allocator keep per-iteration copies alive and spill
-  // 142 VGPRs in the fused variants (measured; the plain variant fit).
+  // Accumulators and the checksums are declared ONCE, outside the tile
+  // loop, and re-zeroed per segment — declaring them inside the loop body
+  // made the allocator keep per-iteration copies alive and spill 142 VGPRs
+  // in the fused variants (measured; the plain variant fit).
   typename T::acc_t acc[FM][FN];
   checksum_regs<FN> cs;
 #pragma unroll
@@ -231,34 +207,14 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
     for (int fn = 0; fn < FN; ++fn) acc[fm][fn] = {};
   cs.clear();
 
-    // verify: the shared detect_partials() and locate_correct() of
-    // csrc/ft_kernels.hpp, as in the classic kernel's verify_correct,
-    // operating on this workgroup's PARTIAL k-range accumulation.
-    // (im0, jn0, kbase) place the segment's tile; p_end is the group's end
-    // panel within the segment and groups start at multiples of ppg panels:
-    // all the fault log needs, and only read in the tripped branch.
-    auto verify_correct = [&](int im0, int jn0, int kbase, int p_end, int ppg)
-        __attribute__((always_inline)) {
-      float cc[FN], cw[FN], pf[FN];
-#pragma unroll
-      for (int fn = 0; fn < FN; ++fn) {
-        cc[fn] = cs.cc(fn);
-        cw[fn] = cs.cw(fn);
-      }
-      const float res = detect_partials<FM, FN, MM>(acc, cc, pf);
-      if (__builtin_expect(fabsf(res) > tau, 0)) {
-        FaultCtx ctx;
-        if constexpr (LOG) {
-          ctx.log = flog;
-          const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-          ctx.i0 = im0 + (wv / WAVES_N) * WM;
-          ctx.j0 = jn0 + (wv % WAVES_N) * WN;
-          ctx.k_begin = kbase + ((p_end - 1) / ppg) * ppg * BK;
-          ctx.k_end = kbase + p_end * BK;
-        }
-        locate_correct<FM, FN, MM, LOG>(acc, cc, cw, pf, sub, tau, ctx);
-      }
-    };
+  // verify this workgroup's PARTIAL k-range accumulation: (im0, jn0, kbase)
+  // place the segment's tile; p_end is the group's end panel within the
+  // segment and groups start at multiples of ppg panels
+  auto verify = [&](int im0, int jn0, int kbase, int p_end, int ppg)
+      __attribute__((always_inline)) {
+    verify_window<G, LOG>(acc, cs, sub, tau, flog, im0, jn0, kbase, p_end,
+                          ppg);
+  };
 
   while (u < u_end) {
     const int tile = u / upt;
@@ -268,12 +224,12 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
     const int w_hi = w_lo + seg_units;
     const int bx = tile % ntm, by = tile / ntm;
     const int im0 = bx * BM, jn0 = by * BN;
-    const int segA = bx * WAVES_M + wm_idx;
+    const int segA = bx * G::WAVES_M + wm_idx;
     const int kbase = w_lo << 6;
     const int npan = seg_units * PPS;
 
     stage(0, kbase, im0, jn0);
-    if constexpr (ABFT) strip_stage(w_lo & 1, kbase, segA);
+    if constexpr (ABFT) stage_strip(w_lo & 1, kbase, segA);
     FT_PARA_SYNC();
     __syncthreads();
 
@@ -293,8 +249,8 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
           stage(qb ^ 1, kbase + (p + 1) * BK, im0, jn0);
           if constexpr (ABFT) {
             if ((p + 1) % PPS == 0)
-              strip_stage((w_lo + (p + 1) / PPS) & 1,
-                          kbase + (p + 1) * BK, segA);
+              stage_strip((w_lo + (p + 1) / PPS) & 1, kbase + (p + 1) * BK,
+                          segA);
           }
         }
         FT_PARA_SYNC();
@@ -304,8 +260,11 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
             ABFT ? &lds[STRIP_OFF + wave * 256 + ((w_lo + p / PPS) & 1) * 128 +
                         (p % PPS) * BK * 2]
                  : nullptr;
-        // strip reads parked, encode behind the barrier: see the classic
-        // kernel's panel loop (ft_kernels.hpp)
+        // The panel body of the classic kernel (ft_kernels.hpp; the comment
+        // there explains the parked strip reads and the encode behind the
+        // barrier).  It stays written out in both kernels: as a shared
+        // function it changed the register counts of most tiers
+        // (docs/ABLATION.md §5e).
         constexpr int NKK = BK / KSTEP;
         constexpr bool DEFER = ABFT && defer_encode<FM, FN>;
         f32x2 swv[DEFER ? NKK : 1];
@@ -342,7 +301,7 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
           for (int kk = 0; kk < NKK; ++kk) cs.encode(swv[kk], bv[kk]);
         }
       }
-      if constexpr (ABFT) verify_correct(im0, jn0, kbase, p, PPG);
+      if constexpr (ABFT) verify(im0, jn0, kbase, p, PPG);
     }
 
     // ---- tile contribution ----
@@ -357,25 +316,14 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
     // partially and hung at N=4608; the same binary was fine once the
     // process had prior GPU activity).  Kernel-boundary ordering makes
     // the partials visible to the fixup kernel with no fences at all.
-    constexpr int TPT = FM * FN * NREG;  // per-thread floats of one tile
     const bool full_seg = (w_lo == 0) && (w_hi == upt);
     if (!full_seg) {
-      float* slot = partials +
-                    ((size_t)(2 * g + (w_lo == 0 ? 1 : 0))) * (BM * BN) +
-                    tid * TPT;
-#pragma unroll
-      for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-        for (int fn = 0; fn < FN; ++fn)
-#pragma unroll
-          for (int g4 = 0; g4 < NREG / 4; ++g4) {
-            f32x4 v;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) v[q4] = acc[fm][fn][4 * g4 + q4];
-            *(f32x4*)(slot + (fm * FN + fn) * NREG + 4 * g4) = v;
-          }
+      store_partial<G>(
+          partial_slot<G>(partials, 2 * g + (w_lo == 0 ? 1 : 0), t.tid), acc);
     } else {
-      // direct alpha/beta epilogue (identical to the classic kernel)
+      // direct alpha/beta epilogue (identical to the classic kernel's and
+      // the fixup kernel's; written out because a shared function changed
+      // which product the compiler fuses into the fma, docs/ABLATION.md §5e)
 #pragma unroll
       for (int fm = 0; fm < FM; ++fm)
 #pragma unroll
@@ -383,7 +331,7 @@ void sgemm_mfma_streamk(int M, int N, int K, const float* __restrict__ A,
           const int j = jn0 + wj0 + fn * MM + r;
           float* colbase = C + (size_t)j * M + im0 + wi0 + fm * MM;
 #pragma unroll
-          for (int g4 = 0; g4 < NREG / 4; ++g4) {
+          for (int g4 = 0; g4 < G::NREG / 4; ++g4) {
             float* p4 = colbase + 4 * sub + 8 * g4;
             f32x4 out;
             if (beta != 0.f) {

@@ -10,6 +10,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "ft_kernels.hpp"
 #include "ft_streamk.hpp"
@@ -61,6 +62,26 @@ int abft_encode(int M, int K, const float* A, float* ws, hipStream_t stream) {
   return sstr;
 }
 
+// The fault log a launch runs with: the caller's when one is attached (fused
+// variants only), none otherwise.  Caller-owned: no allocation, no sync, so
+// the launch stays legal under graph capture.
+inline FaultLog attached_log(bool abft, const FaultLog* log) {
+  return (abft && log && log->counters) ? *log : FaultLog{};
+}
+
+// Picks one variant of a kernel family (all share one signature): the plain
+// kernel, or the fused twin with or without the injector.  With a log
+// attached (`logged`) the LOG twin runs; without one, the unlogged kernel.
+// fused(inj, lg) hands out the <ABFT, INJECT = inj, LOG = lg> instantiation.
+template <class K, class F>
+K select_variant(bool abft, bool inject, bool logged, K plain, F fused) {
+  using Y = std::true_type;
+  using N = std::false_type;
+  if (!abft) return plain;
+  if (logged) return inject ? fused(Y{}, Y{}) : fused(N{}, Y{});
+  return inject ? fused(Y{}, N{}) : fused(N{}, N{});
+}
+
 inline int device_cu_count() {
   static int cus = [] {
     int dev = 0, n = 0;
@@ -86,27 +107,25 @@ hipError_t launch_tier_streamk_t(bool abft, bool inject, int M, int N, int K,
   if (M % BM || N % BN || K % 64 || K % (abft ? BKF : BK) || M % 4 ||
       N % 4)
     return hipErrorNotSupported;
-  constexpr int THREADS = 64 * (BM / WM) * (BN / WN);
+  constexpr int THREADS = tile_geom<BM, BN, BK, WM, WN, MM, false>::THREADS;
 
-  // the three variants share one signature: select once, for both the
-  // occupancy query and the launch
-  const auto kfn =
-      abft ? (inject ? &sgemm_mfma_streamk<BM, BN, BKF, WM, WN, MM, true, true>
-                     : &sgemm_mfma_streamk<BM, BN, BKF, WM, WN, MM, true,
-                                           false>)
-           : &sgemm_mfma_streamk<BM, BN, BK, WM, WN, MM, false, false>;
-  // The fault-log twins (LOG) of the fused variants.  The occupancy query,
-  // and with it the classic/stream-K decision and the grid G, always uses
-  // the unlogged kernel: attaching a log must not change the decomposition
-  // (and so the summation order of C).  Nothing needs G co-resident.
-  const FaultLog flog = (abft && log && log->counters) ? *log : FaultLog{};
-  const auto kfn_launch =
-      !flog.counters
-          ? kfn
-          : (inject ? &sgemm_mfma_streamk<BM, BN, BKF, WM, WN, MM, true, true,
-                                          2, true>
-                    : &sgemm_mfma_streamk<BM, BN, BKF, WM, WN, MM, true,
-                                          false, 2, true>);
+  // The occupancy query, and with it the classic/stream-K decision and the
+  // grid G, always uses the unlogged kernel: attaching a log must not change
+  // the decomposition (and so the summation order of C).  Nothing needs G
+  // co-resident.
+  const FaultLog flog = attached_log(abft, log);
+  const auto variant = [&](bool logged) {
+    return select_variant(
+        abft, inject, logged,
+        &sgemm_mfma_streamk<BM, BN, BK, WM, WN, MM, false, false>,
+        [](auto inj, auto lg) {
+          return &sgemm_mfma_streamk<BM, BN, BKF, WM, WN, MM, true,
+                                     decltype(inj)::value, 2,
+                                     decltype(lg)::value>;
+        });
+  };
+  const auto kfn = variant(false);
+  const auto kfn_launch = variant(flog.counters != nullptr);
   int maxblk = 0;
   const hipError_t oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(
       &maxblk, (const void*)kfn, THREADS, 0);
@@ -235,7 +254,7 @@ hipError_t launch_tier(bool abft, bool inject, int M, int N, int K,
   if (M % BM || N % BN || K % bk_used || M % 4 || N % 4)
     return hipErrorInvalidValue;
   dim3 grid(M / BM, N / BN);
-  dim3 block(64 * (BM / WM) * (BN / WN));
+  dim3 block(tile_geom<BM, BN, BK, WM, WN, MM, false>::THREADS);
   const int niter = K / bk_used;
   // ~20 verify/inject windows per GEMM (reference period K/20,
   // ft_sgemm_huge.cuh:324-327), whole BK panels; plain kernels run one
@@ -252,33 +271,16 @@ hipError_t launch_tier(bool abft, bool inject, int M, int N, int K,
   }
   RoctxRange rr_main(abft ? (inject ? "ft_sgemm_abft_inject" : "ft_sgemm_abft")
                           : "sgemm_plain");
-  // caller-owned fault log, fused variants only: no allocation, no sync, so
-  // the launch stays legal under graph capture.  With a log attached the
-  // LOG twin runs; without one, the unlogged kernel.
-  const FaultLog flog = (abft && log && log->counters) ? *log : FaultLog{};
-  if (flog.counters && inject) {
-    hipLaunchKernelGGL(
-        (sgemm_mfma<BM, BN, BKF, WM, WN, MM, true, true, 2, true>), grid,
-        block, 0, stream, M, N, K, A, B, C, alpha, beta, stride, stride, tau,
-        inj_mag, SA, sstr, flog);
-  } else if (flog.counters) {
-    hipLaunchKernelGGL(
-        (sgemm_mfma<BM, BN, BKF, WM, WN, MM, true, false, 2, true>), grid,
-        block, 0, stream, M, N, K, A, B, C, alpha, beta, stride, stride, tau,
-        inj_mag, SA, sstr, flog);
-  } else if (abft && inject) {
-    hipLaunchKernelGGL((sgemm_mfma<BM, BN, BKF, WM, WN, MM, true, true>), grid,
-                       block, 0, stream, M, N, K, A, B, C, alpha, beta,
-                       stride, stride, tau, inj_mag, SA, sstr, flog);
-  } else if (abft) {
-    hipLaunchKernelGGL((sgemm_mfma<BM, BN, BKF, WM, WN, MM, true, false>),
-                       grid, block, 0, stream, M, N, K, A, B, C, alpha, beta,
-                       stride, stride, tau, inj_mag, SA, sstr, flog);
-  } else {
-    hipLaunchKernelGGL((sgemm_mfma<BM, BN, BK, WM, WN, MM, false, false>),
-                       grid, block, 0, stream, M, N, K, A, B, C, alpha, beta,
-                       stride, stride, tau, inj_mag, SA, sstr, flog);
-  }
+  const FaultLog flog = attached_log(abft, log);
+  const auto kfn = select_variant(
+      abft, inject, flog.counters != nullptr,
+      &sgemm_mfma<BM, BN, BK, WM, WN, MM, false, false>,
+      [](auto inj, auto lg) {
+        return &sgemm_mfma<BM, BN, BKF, WM, WN, MM, true, decltype(inj)::value,
+                           2, decltype(lg)::value>;
+      });
+  hipLaunchKernelGGL(kfn, grid, block, 0, stream, M, N, K, A, B, C, alpha,
+                     beta, stride, stride, tau, inj_mag, SA, sstr, flog);
   return hipGetLastError();
 }
 

@@ -246,6 +246,26 @@ def test_streamk_multi_tile_ranges_alpha_beta(monkeypatch, capfd):
 
 
 @gpu
+@pytest.mark.parametrize("variant", ["plain", "fused", "inject"])
+@pytest.mark.parametrize("tier", ["huge", "large"])
+def test_streamk_two_by_two_tiles(monkeypatch, capfd, tier, variant):
+    """Forced stream-K at M = 2 BM, N = 2 BN, K = 256: 4 tiles x 4 units over
+    G = 3 workgroups (6/5/5 units) gives fully-owned tiles, head partials and
+    tail partials, crossing the tile indexing, both strip buffers and both
+    fixup slots of the staging and epilogue code the two kernels share."""
+    t = TILING[tier]
+    m, n = 2 * t["bm"], 2 * t["bn"]
+    run = _plain(tier) if variant == "plain" else _fused(tier,
+                                                        variant == "inject")
+    v = (functools.partial(streamk_v, tier, m, n) if variant == "inject"
+         else None)
+    path = Path(f"streamk-{tier}-{variant}-2x2", (m, n, 256),
+                {"FT_SGEMM_STREAMK": "1", "FT_SGEMM_SK_G": "3",
+                 "FT_SGEMM_SK_DEBUG": "1"}, run, v, engaged=True)
+    _run_and_check(monkeypatch, capfd, path, -2.0, 1.0)
+
+
+@gpu
 @pytest.mark.parametrize("fill", [float("nan"), float("inf")],
                          ids=["nan", "inf"])
 @pytest.mark.parametrize("path", PATHS, ids=_ids)
