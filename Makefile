@@ -13,12 +13,14 @@ cli: bin/ft_sgemm
 # filter out PyTorch-hipify byproducts (kernel_*_hip.hip copies)
 KERNEL_TUS := $(filter-out %_hip.hip, $(wildcard csrc/generated/kernel_*.hip))
 
-bin/ft_sgemm: csrc/cli_main.hip csrc/dispatch.hip csrc/rocblas_path.hip csrc/locate_selftest.hip csrc/ft_kernels.hpp csrc/ft_streamk.hpp csrc/tier_launch.hpp csrc/ft_core.h csrc/fault_log.h csrc/generated/tile_params.h $(KERNEL_TUS)
+CLI_SRCS := csrc/cli_main.hip csrc/dispatch.hip csrc/rocblas_path.hip \
+            csrc/locate_selftest.hip $(KERNEL_TUS)
+CLI_HIPCC = $(HIPCC) -x hip --offload-arch=$(ARCH) -O3 -std=c++17 -Icsrc
+CLI_LIBS := -L$(ROCM)/lib -lrocblas -lroctx64
+
+bin/ft_sgemm: $(CLI_SRCS) csrc/ft_kernels.hpp csrc/ft_streamk.hpp csrc/tier_launch.hpp csrc/ft_core.h csrc/fault_log.h csrc/generated/tile_params.h
 	mkdir -p bin
-	$(HIPCC) -x hip --offload-arch=$(ARCH) -O3 -std=c++17 -Icsrc $(FTFLAGS) \
-	  csrc/cli_main.hip csrc/dispatch.hip csrc/rocblas_path.hip \
-	  csrc/locate_selftest.hip $(KERNEL_TUS) \
-	  -L$(ROCM)/lib -lrocblas -lroctx64 -o $@
+	$(CLI_HIPCC) $(FTFLAGS) $(CLI_SRCS) $(CLI_LIBS) -o $@
 
 # Paranoid-sync build for the race check (tools/race_check.sh): every
 # async-staging site gets an immediate full vmcnt/lgkm drain + barrier;
@@ -26,10 +28,7 @@ bin/ft_sgemm: csrc/cli_main.hip csrc/dispatch.hip csrc/rocblas_path.hip csrc/loc
 # arithmetic order) — any difference indicates a staging race.
 cli-paranoid:
 	mkdir -p bin
-	$(HIPCC) -x hip --offload-arch=$(ARCH) -O3 -std=c++17 -Icsrc -DFT_PARANOID \
-	  csrc/cli_main.hip csrc/dispatch.hip csrc/rocblas_path.hip \
-	  csrc/locate_selftest.hip $(KERNEL_TUS) \
-	  -L$(ROCM)/lib -lrocblas -lroctx64 -o bin/ft_sgemm_paranoid
+	$(CLI_HIPCC) -DFT_PARANOID $(CLI_SRCS) $(CLI_LIBS) -o bin/ft_sgemm_paranoid
 
 ext:
 	# ninja does not track header deps for hipcc sources: rebuild .hip TUs

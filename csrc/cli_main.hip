@@ -65,16 +65,16 @@ bool run_kernel(int kid, int M, int N, int K, const float* dA,
                 const float* dB, float* dC, float alpha, float beta,
                 const ftsgemm::BaselineWorkspace& ws, bool inject,
                 const ftsgemm::FaultLog* log = nullptr) {
+  ftsgemm::GemmArgs g{/*abft=*/false, /*inject=*/false, M, N, K, dA, dB, dC,
+                      alpha, beta, kTau, kInj, /*verify_windows=*/20};
   if (kid >= 1 && kid <= 6)
-    return ftsgemm::sgemm_tier_launch(kid - 1, false, false, M, N, K, dA, dB,
-                                      dC, alpha, beta, kTau, kInj, 20,
-                                      nullptr, 0) == hipSuccess;
+    return ftsgemm::sgemm_tier_launch(kid - 1, g) == hipSuccess;
   if (kid >= 11 && kid <= 16) {
-    float* w = abft_ws(
-        ftsgemm::sgemm_abft_workspace_floats(kid - 11, M, N, K));
-    return ftsgemm::sgemm_tier_launch(kid - 11, true, inject, M, N, K, dA,
-                                      dB, dC, alpha, beta, kTau, kInj, 20,
-                                      w, 0, log) == hipSuccess;
+    g.abft = true;
+    g.inject = inject;
+    g.ws = abft_ws(ftsgemm::sgemm_abft_workspace_floats(kid - 11, M, N, K));
+    g.log = log;
+    return ftsgemm::sgemm_tier_launch(kid - 11, g) == hipSuccess;
   }
   if (kid == 10) {
     // panel width sized for MI355X (the reference's 256 is T4-sized: at

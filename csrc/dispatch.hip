@@ -11,58 +11,49 @@
 
 namespace ftsgemm {
 
-#define FT_DECL(name, BM, BN, BK, WM, WN, MM)                               \
-  hipError_t launch_tier_##name(bool abft, bool inject, int M, int N, int K, \
-                                const float* A, const float* B, float* C,    \
-                                float alpha, float beta, float tau,          \
-                                float inj_mag, int verify_windows, float* ws,\
-                                hipStream_t stream, const FaultLog* log);    \
+#define FT_DECL(name, BM, BN, BK, WM, WN, MM)      \
+  hipError_t launch_tier_##name(const GemmArgs& g); \
   size_t abft_ws_floats_##name(int M, int N, int K);
 FT_TIER_LIST(FT_DECL)
 #undef FT_DECL
 
-hipError_t sgemm_tier_launch(int tier, bool abft, bool inject, int M, int N,
-                             int K, const float* A, const float* B, float* C,
-                             float alpha, float beta, float tau,
-                             float inj_mag, int verify_windows, float* ws,
-                             hipStream_t stream, const FaultLog* log) {
-  switch (tier) {
-#define FT_CASE(name, BM, BN, BK, WM, WN, MM)                              \
-  case FT_TIER_ID_##name:                                                  \
-    return launch_tier_##name(abft, inject, M, N, K, A, B, C, alpha, beta, \
-                              tau, inj_mag, verify_windows, ws, stream,    \
-                              log);
-    FT_TIER_LIST(FT_CASE)
-#undef FT_CASE
-    default:
-      return hipErrorInvalidValue;
-  }
+namespace {
+
+// One row per tier, in FT_TIER_LIST order: the generator numbers
+// FT_TIER_ID_<name> by position in that list, so a tier id indexes the table.
+struct TierRow {
+  hipError_t (*launch)(const GemmArgs&);
+  size_t (*ws_floats)(int, int, int);
+  int bm, bn, bk;
+};
+const TierRow kTiers[FT_N_TIERS] = {
+#define FT_ROW(name, BM, BN, BK, WM, WN, MM) \
+  {launch_tier_##name, abft_ws_floats_##name, BM, BN, BK},
+    FT_TIER_LIST(FT_ROW)
+#undef FT_ROW
+};
+
+const TierRow* tier_row(int tier) {
+  return tier >= 0 && tier < FT_N_TIERS ? &kTiers[tier] : nullptr;
 }
 
-// Workspace floats needed by the fused-ABFT path of a tier (segment-sum
-// matrices SA+SB); 0 for plain kernels.
+}  // namespace
+
+hipError_t sgemm_tier_launch(int tier, const GemmArgs& g) {
+  const TierRow* t = tier_row(tier);
+  return t ? t->launch(g) : hipErrorInvalidValue;
+}
+
+// Workspace floats needed by the fused-ABFT path of a tier (the segment-sum
+// matrix SA).
 size_t sgemm_abft_workspace_floats(int tier, int M, int N, int K) {
-  switch (tier) {
-#define FT_WS(name, BM, BN, BK, WM, WN, MM) \
-  case FT_TIER_ID_##name:                   \
-    return abft_ws_floats_##name(M, N, K);
-    FT_TIER_LIST(FT_WS)
-#undef FT_WS
-    default:
-      return 0;
-  }
+  const TierRow* t = tier_row(tier);
+  return t ? t->ws_floats(M, N, K) : 0;
 }
 
 bool sgemm_tier_supported(int tier, int M, int N, int K) {
-  switch (tier) {
-#define FT_CHK(name, BM, BN, BK, WM, WN, MM)                               \
-  case FT_TIER_ID_##name:                                                  \
-    return !(M % BM || N % BN || K % BK || M % 4 || N % 4);
-    FT_TIER_LIST(FT_CHK)
-#undef FT_CHK
-    default:
-      return false;
-  }
+  const TierRow* t = tier_row(tier);
+  return t && !(M % t->bm || N % t->bn || K % t->bk || M % 4 || N % 4);
 }
 
 }  // namespace ftsgemm

@@ -8,60 +8,78 @@
 
 namespace ftsgemm {
 
-// Launch one of the six hand-tiled MFMA SGEMM kernels (tier id per
-// generated/tile_params.h; abft selects the fused-ABFT twin, inject the
-// always-on fault injector).  C = alpha*A*B^T + beta*C, column-major.
+// One launch of the hand-tiled MFMA SGEMM kernels, host side only (never a
+// kernel argument): C = alpha*A*B^T + beta*C, column-major.  abft selects
+// the fused-ABFT twin, inject the always-on fault injector.
 // When abft, `ws` must point to a device scratch buffer of
 // sgemm_abft_workspace_floats(tier, M, N, K) fp32 elements (the launcher
-// fills it with the segment checksums of A and B before the fused kernel).
+// fills it with the segment checksums of A before the fused kernel).
 // `log` (optional, fused variants only) attaches a caller-owned fault log
 // (fault_log.h): the kernels' locate/correct path adds to its counters and
 // appends one event per detected fault.  The launch neither zeroes,
 // allocates nor syncs for it — counts accumulate until the caller clears
 // them — and with log == nullptr the kernels write nothing.
-hipError_t sgemm_tier_launch(int tier, bool abft, bool inject, int M, int N,
-                             int K, const float* A, const float* B, float* C,
-                             float alpha, float beta, float tau,
-                             float inj_mag, int verify_windows, float* ws,
-                             hipStream_t stream,
-                             const FaultLog* log = nullptr);
+struct GemmArgs {
+  bool abft, inject;
+  int M, N, K;
+  const float *A, *B;
+  float* C;
+  float alpha, beta, tau, inj_mag;
+  int verify_windows;  // <= 0: the default of 20
+  float* ws = nullptr;
+  hipStream_t stream = 0;
+  const FaultLog* log = nullptr;
+};
+
+// Launch tier `tier` (id per generated/tile_params.h).
+hipError_t sgemm_tier_launch(int tier, const GemmArgs& g);
 
 bool sgemm_tier_supported(int tier, int M, int N, int K);
 
 size_t sgemm_abft_workspace_floats(int tier, int M, int N, int K);
 
-// Device self-test of the fused kernels' shared locate/correct
+// Device self-test of the fused kernels' shared detect / locate / correct
 // (locate_selftest.hip): one single-wave block per case plants up to two
 // accumulator faults in a synthetic FM x FN fragment tile of MM-wide MFMA
-// fragments and corrects it with both the shipped function and the
-// sweep-everything reference form.  idesc: 9 ints per case {nfault,
-// (fm, fn, reg, lane) x 2}; fdesc: 3 floats per case {mag0, mag1, tau};
-// out: [3][ncases][FM*FN*NREG][64] floats = {shipped, reference, clean}.
+// fragments, NREG accumulators per lane each, and runs one of three modes
+// on it.  All outputs are fp32, element e = (fm*FN + fn)*NREG + reg, lane
+// fastest.
+enum SelftestMode {
+  // Corrects the tile with both the shipped locate_correct and the
+  // sweep-everything reference form.
+  // out: [3][ncases][FM*FN*NREG][64] = {shipped, reference, clean}.
+  SELFTEST_LOCATE,
+  // Only the shipped locate_correct, in its fault-log form.  Every case has
+  // a log of its own: counters is [ncases][FLOG_N_COUNTERS] and events
+  // [ncases][capacity][FLOG_EVENT_DWORDS] int32, both zeroed by the caller;
+  // the wave tile sits at origin (0, 0) with k range [0, 0).
+  // out: [ncases][FM*FN*NREG][64], the corrected tile.
+  SELFTEST_REPORT,
+  // Only the shared detect and the locate's fp32 screen; nothing is
+  // corrected.  out: [ncases][FM*FN*NREG + 1 + 2*FN][64]: the faulty tile as
+  // the detect saw it, the wave residual (the same in every lane), per fn
+  // the lane's partial sum p[fn], per fn 1.0 / 0.0 for a screen that passed
+  // / did not (wave-uniform).
+  SELFTEST_DETECT,
+};
+
+// idesc: 9 ints per case {nfault, (fm, fn, reg, lane) x 2}; fdesc: 3 floats
+// per case {mag0, mag1, tau}; clean accumulators are a hash in (-amp, amp).
 // All pointers are device pointers; (fm, fn, mm) must be a tier's shape.
-hipError_t locate_selftest_launch(int fm, int fn, int mm, int ncases,
-                                  const int* idesc, const float* fdesc,
-                                  float amp, float* out, hipStream_t stream);
+// counters / events / capacity: SELFTEST_REPORT only.
+struct SelftestArgs {
+  int fm, fn, mm, ncases;
+  const int* idesc;
+  const float* fdesc;
+  float amp;
+  float* out;
+  int* counters = nullptr;
+  int* events = nullptr;
+  int capacity = 0;
+  hipStream_t stream = 0;
+};
 
-// Report variant of the self-test: runs only the shipped locate_correct, in
-// its fault-log form, on the same descriptors.  Every case has a log of its
-// own: counters is [ncases][FLOG_N_COUNTERS] and events
-// [ncases][capacity][FLOG_EVENT_DWORDS] int32, both zeroed by the caller;
-// the wave tile sits at origin (0, 0) with k range [0, 0).
-// out: [ncases][FM*FN*NREG][64] floats, the corrected tile.
-hipError_t locate_selftest_report_launch(int fm, int fn, int mm, int ncases,
-                                         const int* idesc, const float* fdesc,
-                                         float amp, float* out, int* counters,
-                                         int* events, int capacity,
-                                         hipStream_t stream);
-
-// Detect variant of the self-test: runs only the fused kernels' shared
-// detect and the locate's fp32 screen on the same descriptors, and returns
-// what they computed.  out: [ncases][FM*FN*NREG + 1 + 2*FN][64] floats, lane
-// fastest: the faulty tile, the wave residual, per fn the lane's partial
-// sum p[fn], per fn 1.0 / 0.0 for a screen that passed / did not.
-hipError_t detect_selftest_launch(int fm, int fn, int mm, int ncases,
-                                  const int* idesc, const float* fdesc,
-                                  float amp, float* out, hipStream_t stream);
+hipError_t selftest_launch(SelftestMode mode, const SelftestArgs& a);
 
 // rocBLAS paths (kernel id 0 oracle and the id-10 non-fused ABFT baseline,
 // reference: cuBLAS at sgemm.cu:108 / include/baseline_ft_sgemm.cuh).

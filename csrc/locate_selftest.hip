@@ -7,12 +7,13 @@
 // the case's fault(s) at arbitrary (fm, fn, reg, lane) sites, and runs both
 // locate_correct and locate_correct_ref, the unscreened sweep-everything
 // form it replaced.  tests/test_gpu_locate_selftest.py asserts the two are
-// bit-identical and that correctable cases restore the clean tile.  The
-// shipped function is driven as the fused kernels drive it: the shared
-// detect (detect_partials) runs first and hands it the per-fn partials.  A
-// third entry runs the detect and the screen alone and returns what they
-// computed (tests/test_gpu_detect_shared.py).
+// bit-identical and that correctable cases restore the clean tile.  A second
+// mode runs the shipped function alone in its fault-log form
+// (tests/test_gpu_fault_report.py); a third runs the detect and the screen
+// alone and returns what they computed (tests/test_gpu_detect_shared.py).
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #include "ft_core.h"
 #include "ft_kernels.hpp"
@@ -72,32 +73,55 @@ __device__ inline float hash_val(unsigned cs, unsigned e, unsigned lane,
   return amp * (2.f * u - 1.f);
 }
 
-// idesc: per case 9 ints  {nfault, fm0, fn0, reg0, lane0, fm1, fn1, reg1,
-//        lane1};  fdesc: per case 3 floats {mag0, mag1, tau}.
-// out:   [3][ncases][FM*FN*NREG][64] = {new, ref, clean} accumulators,
-//        element e = (fm*FN + fn)*NREG + reg, lane fastest.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+
+// One case of the self-test, as every mode sees it: the decoded descriptor
+// (idesc: per case 9 ints {nfault, fm0, fn0, reg0, lane0, fm1, fn1, reg1,
+// lane1}; fdesc: per case 3 floats {mag0, mag1, tau}), this lane's slice of
+// the synthetic FM x FN tile and its checksum partials.  One tile is live at
+// a time (three would not fit the register file at FM*FN*NREG = 128): it is
+// refilled from the hash for each pass.  Faults are planted by comparison,
+// never by dynamic register indexing.
 template <int FM, int FN, int MM>
-__global__ __launch_bounds__(64) void locate_selftest_kernel(
-    int ncases, const int* __restrict__ idesc,
-    const float* __restrict__ fdesc, float amp, float* __restrict__ out) {
+struct SelftestCase {
   using T = mfma_traits<MM>;
-  constexpr int NREG = T::nreg;
-  constexpr int E = FM * FN * NREG;
-  const int cs = blockIdx.x;
-  if (cs >= ncases) return;
-  const int lane = threadIdx.x;
-  const int sub = lane / MM;
+  static constexpr int NREG = T::nreg;
+  static constexpr int E = FM * FN * NREG;  // e = (fm*FN + fn)*NREG + reg
 
-  const int* id = idesc + (size_t)cs * 9;
-  const float* fd = fdesc + (size_t)cs * 3;
-  const int nf = id[0];
-  const float tau = fd[2];
-
-  // One tile is live at a time (three would not fit the register file at
-  // FM*FN*NREG = 128): it is refilled from the hash for each pass.  Faults
-  // are planted by comparison, never by dynamic register indexing.
+  int cs, lane, sub, nf;
+  const int* id;
+  const float* fd;
+  float amp, tau;
   typename T::acc_t tile[FM][FN];
-  auto fill = [&](bool faulty) __attribute__((always_inline)) {
+  float cc[FN], cw[FN];
+
+  // Leaves the clean tile live and its checksum partials in cc / cw, summed
+  // in the opposite order to the locate's own sums, so the clean residual is
+  // fp32 rounding noise and not exactly zero.
+  __device__ __forceinline__ SelftestCase(int cs_, const int* idesc,
+                                          const float* fdesc, float amp_)
+      : cs(cs_), lane(threadIdx.x), sub(lane / MM),
+        id(idesc + (size_t)cs_ * 9), fd(fdesc + (size_t)cs_ * 3), amp(amp_) {
+    nf = id[0];
+    tau = fd[2];
+    fill(false);
+#pragma unroll
+    for (int fn = 0; fn < FN; ++fn) {
+      cc[fn] = 0.f;
+      cw[fn] = 0.f;
+#pragma unroll
+      for (int fm = FM - 1; fm >= 0; --fm)
+#pragma unroll
+        for (int reg = NREG - 1; reg >= 0; --reg) {
+          const float v = tile[fm][fn][reg];
+          cc[fn] += v;
+          cw[fn] = fmaf((float)(fm * MM + acc_row(reg, sub)), v, cw[fn]);
+        }
+    }
+  }
+
+  __device__ __forceinline__ void fill(bool faulty) {
 #pragma unroll
     for (int fm = 0; fm < FM; ++fm)
 #pragma unroll
@@ -113,10 +137,11 @@ __global__ __launch_bounds__(64) void locate_selftest_kernel(
           }
           tile[fm][fn][reg] = v;
         }
-  };
-  const size_t plane = (size_t)ncases * E * 64;
-  auto store = [&](int which) __attribute__((always_inline)) {
-    float* o = out + which * plane + (size_t)cs * E * 64 + lane;
+  }
+
+  // The live tile to dst[E][64], lane fastest.
+  __device__ __forceinline__ void store(float* dst) const {
+    float* o = dst + lane;
 #pragma unroll
     for (int fm = 0; fm < FM; ++fm)
 #pragma unroll
@@ -124,274 +149,103 @@ __global__ __launch_bounds__(64) void locate_selftest_kernel(
 #pragma unroll
         for (int reg = 0; reg < NREG; ++reg)
           o[(size_t)((fm * FN + fn) * NREG + reg) * 64] = tile[fm][fn][reg];
-  };
-
-  // clean tile -> this lane's checksum partials, in the opposite summation
-  // order to the locate's own sums, so the clean residual is fp32 rounding
-  // noise and not exactly zero
-  fill(false);
-  store(2);
-  float cc[FN], cw[FN];
-#pragma unroll
-  for (int fn = 0; fn < FN; ++fn) {
-    cc[fn] = 0.f;
-    cw[fn] = 0.f;
-#pragma unroll
-    for (int fm = FM - 1; fm >= 0; --fm)
-#pragma unroll
-      for (int reg = NREG - 1; reg >= 0; --reg) {
-        const float v = tile[fm][fn][reg];
-        cc[fn] += v;
-        cw[fn] = fmaf((float)(fm * MM + acc_row(reg, sub)), v, cw[fn]);
-      }
   }
+};
 
-  // as the fused kernels do: the detect's partials feed the locate's screen
-  fill(true);
-  float p[FN];
-  (void)detect_partials<FM, FN, MM>(tile, cc, p);
-  locate_correct<FM, FN, MM>(tile, cc, cw, p, sub, tau);
-  store(0);
-  fill(true);
-  locate_correct_ref<FM, FN, MM>(tile, cc, cw, sub, tau);
-  store(1);
-}
-
-// Report variant: only the shipped locate_correct, in its fault-log (LOG)
-// form, on the same case descriptors.  Every case owns a log of its own —
-// counters + cs*FLOG_N_COUNTERS, events + cs*capacity*FLOG_EVENT_DWORDS —
-// with the wave tile at origin (0, 0) and the k range [0, 0).
-// out: [ncases][FM*FN*NREG][64], the corrected tile.
-template <int FM, int FN, int MM>
-__global__ __launch_bounds__(64) void locate_selftest_report_kernel(
+// One single-wave block per case; what MODE runs on the case and what it
+// writes to `out` is documented at SelftestMode (ft_core.h).  Every mode
+// drives the shipped code as the fused kernels do: the shared detect
+// (detect_partials) runs first and hands the locate its per-fn partials.
+// counters / events / capacity are read by SELFTEST_REPORT only.
+template <int FM, int FN, int MM, SelftestMode MODE>
+__global__ __launch_bounds__(64) void selftest_kernel(
     int ncases, const int* __restrict__ idesc,
     const float* __restrict__ fdesc, float amp, float* __restrict__ out,
     int* __restrict__ counters, int* __restrict__ events, int capacity) {
-  using T = mfma_traits<MM>;
-  constexpr int NREG = T::nreg;
-  constexpr int E = FM * FN * NREG;
   const int cs = blockIdx.x;
   if (cs >= ncases) return;
-  const int lane = threadIdx.x;
-  const int sub = lane / MM;
-
-  const int* id = idesc + (size_t)cs * 9;
-  const float* fd = fdesc + (size_t)cs * 3;
-  const int nf = id[0];
-  const float tau = fd[2];
-
-  typename T::acc_t tile[FM][FN];
-  auto fill = [&](bool faulty) __attribute__((always_inline)) {
-#pragma unroll
-    for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-      for (int fn = 0; fn < FN; ++fn)
-#pragma unroll
-        for (int reg = 0; reg < NREG; ++reg) {
-          float v = hash_val(cs, (fm * FN + fn) * NREG + reg, lane, amp);
-          for (int f = 0; f < 2; ++f) {
-            const int* s = id + 1 + 4 * f;
-            if (faulty && f < nf && s[0] == fm && s[1] == fn &&
-                s[2] == reg && s[3] == lane)
-              v += fd[f];
-          }
-          tile[fm][fn][reg] = v;
-        }
-  };
-
-  // same checksum construction as locate_selftest_kernel
-  fill(false);
-  float cc[FN], cw[FN];
-#pragma unroll
-  for (int fn = 0; fn < FN; ++fn) {
-    cc[fn] = 0.f;
-    cw[fn] = 0.f;
-#pragma unroll
-    for (int fm = FM - 1; fm >= 0; --fm)
-#pragma unroll
-      for (int reg = NREG - 1; reg >= 0; --reg) {
-        const float v = tile[fm][fn][reg];
-        cc[fn] += v;
-        cw[fn] = fmaf((float)(fm * MM + acc_row(reg, sub)), v, cw[fn]);
-      }
-  }
-
-  fill(true);
-  FaultCtx ctx;
-  ctx.log.counters = counters + (size_t)cs * FLOG_N_COUNTERS;
-  ctx.log.events = events + (size_t)cs * capacity * FLOG_EVENT_DWORDS;
-  ctx.log.capacity = capacity;
+  SelftestCase<FM, FN, MM> c(cs, idesc, fdesc, amp);
+  constexpr int E = decltype(c)::E;
   float p[FN];
-  (void)detect_partials<FM, FN, MM>(tile, cc, p);
-  locate_correct<FM, FN, MM, true>(tile, cc, cw, p, sub, tau, ctx);
-  float* o = out + (size_t)cs * E * 64 + lane;
+  if constexpr (MODE == SELFTEST_LOCATE) {
+    const size_t plane = (size_t)ncases * E * 64;
+    float* o = out + (size_t)cs * E * 64;
+    c.store(o + 2 * plane);
+    c.fill(true);
+    (void)detect_partials<FM, FN, MM>(c.tile, c.cc, p);
+    locate_correct<FM, FN, MM>(c.tile, c.cc, c.cw, p, c.sub, c.tau);
+    c.store(o);
+    c.fill(true);
+    locate_correct_ref<FM, FN, MM>(c.tile, c.cc, c.cw, c.sub, c.tau);
+    c.store(o + plane);
+  } else if constexpr (MODE == SELFTEST_REPORT) {
+    c.fill(true);
+    FaultCtx ctx;
+    ctx.log.counters = counters + (size_t)cs * FLOG_N_COUNTERS;
+    ctx.log.events = events + (size_t)cs * capacity * FLOG_EVENT_DWORDS;
+    ctx.log.capacity = capacity;
+    (void)detect_partials<FM, FN, MM>(c.tile, c.cc, p);
+    locate_correct<FM, FN, MM, true>(c.tile, c.cc, c.cw, p, c.sub, c.tau, ctx);
+    c.store(out + (size_t)cs * E * 64);
+  } else {
+    c.fill(true);
+    const float res = detect_partials<FM, FN, MM>(c.tile, c.cc, p);
+    float* o = out + (size_t)cs * (E + 1 + 2 * FN) * 64;
+    c.store(o);
+    o += c.lane;
+    o[(size_t)E * 64] = res;
 #pragma unroll
-  for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-    for (int fn = 0; fn < FN; ++fn)
-#pragma unroll
-      for (int reg = 0; reg < NREG; ++reg)
-        o[(size_t)((fm * FN + fn) * NREG + reg) * 64] = tile[fm][fn][reg];
+    for (int fn = 0; fn < FN; ++fn) {
+      o[(size_t)(E + 1 + fn) * 64] = p[fn];
+      o[(size_t)(E + 1 + FN + fn) * 64] =
+          screen_passes<MM>(p[fn], c.cc[fn], c.tau) ? 1.f : 0.f;
+    }
+  }
 }
 
-// Detect variant: the shared detect (detect_partials) and the locate's
-// screen (screen_passes) alone, on the same case descriptors and the same
-// tile and checksum construction.  Nothing is corrected.
-// out: [ncases][FM*FN*NREG + 1 + 2*FN][64] floats, lane fastest: the faulty
-//      tile as the detect saw it, then the residual (the same in every lane),
-//      then per fn this lane's partial p[fn], then per fn 1.0 / 0.0 for a
-//      screen that passed / did not (wave-uniform).
-template <int FM, int FN, int MM>
-__global__ __launch_bounds__(64) void detect_selftest_kernel(
-    int ncases, const int* __restrict__ idesc,
-    const float* __restrict__ fdesc, float amp, float* __restrict__ out) {
-  using T = mfma_traits<MM>;
-  constexpr int NREG = T::nreg;
-  constexpr int E = FM * FN * NREG;
-  constexpr int ROWS = E + 1 + 2 * FN;
-  const int cs = blockIdx.x;
-  if (cs >= ncases) return;
-  const int lane = threadIdx.x;
-
-  const int* id = idesc + (size_t)cs * 9;
-  const float* fd = fdesc + (size_t)cs * 3;
-  const int nf = id[0];
-  const float tau = fd[2];
-
-  typename T::acc_t tile[FM][FN];
-  auto fill = [&](bool faulty) __attribute__((always_inline)) {
-#pragma unroll
-    for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-      for (int fn = 0; fn < FN; ++fn)
-#pragma unroll
-        for (int reg = 0; reg < NREG; ++reg) {
-          float v = hash_val(cs, (fm * FN + fn) * NREG + reg, lane, amp);
-          for (int f = 0; f < 2; ++f) {
-            const int* s = id + 1 + 4 * f;
-            if (faulty && f < nf && s[0] == fm && s[1] == fn &&
-                s[2] == reg && s[3] == lane)
-              v += fd[f];
-          }
-          tile[fm][fn][reg] = v;
-        }
+// Calls f(FM, FN, MM) as integral constants for the wave-tile fragment shape
+// (fm, fn, mm) of one of the six tiers; any other shape is an error and f is
+// not called.
+template <class F>
+hipError_t with_tile_shape(int fm, int fn, int mm, F f) {
+  const auto is = [&](int a, int b, int c) {
+    return fm == a && fn == b && mm == c;
   };
-
-  // same checksum construction as locate_selftest_kernel
-  fill(false);
-  float cc[FN];
-#pragma unroll
-  for (int fn = 0; fn < FN; ++fn) {
-    cc[fn] = 0.f;
-#pragma unroll
-    for (int fm = FM - 1; fm >= 0; --fm)
-#pragma unroll
-      for (int reg = NREG - 1; reg >= 0; --reg) cc[fn] += tile[fm][fn][reg];
-  }
-
-  fill(true);
-  float p[FN];
-  const float res = detect_partials<FM, FN, MM>(tile, cc, p);
-  float* o = out + (size_t)cs * ROWS * 64 + lane;
-#pragma unroll
-  for (int fm = 0; fm < FM; ++fm)
-#pragma unroll
-    for (int fn = 0; fn < FN; ++fn)
-#pragma unroll
-      for (int reg = 0; reg < NREG; ++reg)
-        o[(size_t)((fm * FN + fn) * NREG + reg) * 64] = tile[fm][fn][reg];
-  o[(size_t)E * 64] = res;
-#pragma unroll
-  for (int fn = 0; fn < FN; ++fn) {
-    o[(size_t)(E + 1 + fn) * 64] = p[fn];
-    o[(size_t)(E + 1 + FN + fn) * 64] =
-        screen_passes<MM>(p[fn], cc[fn], tau) ? 1.f : 0.f;
-  }
+  if (is(4, 2, 32)) return f(int_c<4>{}, int_c<2>{}, int_c<32>{});
+  if (is(2, 1, 32)) return f(int_c<2>{}, int_c<1>{}, int_c<32>{});
+  if (is(1, 2, 32)) return f(int_c<1>{}, int_c<2>{}, int_c<32>{});
+  if (is(1, 1, 32)) return f(int_c<1>{}, int_c<1>{}, int_c<32>{});
+  if (is(1, 1, 16)) return f(int_c<1>{}, int_c<1>{}, int_c<16>{});
+  return hipErrorInvalidValue;
 }
 
-template <int FM, int FN, int MM>
-hipError_t launch_detect_selftest(int ncases, const int* idesc,
-                                  const float* fdesc, float amp, float* out,
-                                  hipStream_t stream) {
-  hipLaunchKernelGGL((detect_selftest_kernel<FM, FN, MM>), dim3(ncases),
-                     dim3(64), 0, stream, ncases, idesc, fdesc, amp, out);
-  return hipGetLastError();
-}
-
-template <int FM, int FN, int MM>
-hipError_t launch_selftest(int ncases, const int* idesc, const float* fdesc,
-                           float amp, float* out, hipStream_t stream) {
-  hipLaunchKernelGGL((locate_selftest_kernel<FM, FN, MM>), dim3(ncases),
-                     dim3(64), 0, stream, ncases, idesc, fdesc, amp, out);
-  return hipGetLastError();
-}
-
-template <int FM, int FN, int MM>
-hipError_t launch_selftest_report(int ncases, const int* idesc,
-                                  const float* fdesc, float amp, float* out,
-                                  int* counters, int* events, int capacity,
-                                  hipStream_t stream) {
-  hipLaunchKernelGGL((locate_selftest_report_kernel<FM, FN, MM>),
-                     dim3(ncases), dim3(64), 0, stream, ncases, idesc, fdesc,
-                     amp, out, counters, events, capacity);
-  return hipGetLastError();
+template <SelftestMode MODE>
+hipError_t launch_selftest(const SelftestArgs& a) {
+  return with_tile_shape(a.fm, a.fn, a.mm, [&](auto FM, auto FN, auto MM) {
+    hipLaunchKernelGGL((selftest_kernel<decltype(FM)::value,
+                                        decltype(FN)::value,
+                                        decltype(MM)::value, MODE>),
+                       dim3(a.ncases), dim3(64), 0, a.stream, a.ncases,
+                       a.idesc, a.fdesc, a.amp, a.out, a.counters, a.events,
+                       a.capacity);
+    return hipGetLastError();
+  });
 }
 
 }  // namespace
 
-hipError_t locate_selftest_report_launch(int fm, int fn, int mm, int ncases,
-                                         const int* idesc, const float* fdesc,
-                                         float amp, float* out, int* counters,
-                                         int* events, int capacity,
-                                         hipStream_t stream) {
-  if (ncases < 1 || capacity < 0 || !counters || (capacity > 0 && !events))
-    return hipErrorInvalidValue;
-#define FT_SELFTEST_REPORT(FM_, FN_, MM_)                                    \
-  if (fm == FM_ && fn == FN_ && mm == MM_)                                   \
-    return launch_selftest_report<FM_, FN_, MM_>(ncases, idesc, fdesc, amp,  \
-                                                 out, counters, events,      \
-                                                 capacity, stream);
-  FT_SELFTEST_REPORT(4, 2, 32)
-  FT_SELFTEST_REPORT(2, 1, 32)
-  FT_SELFTEST_REPORT(1, 2, 32)
-  FT_SELFTEST_REPORT(1, 1, 32)
-  FT_SELFTEST_REPORT(1, 1, 16)
-#undef FT_SELFTEST_REPORT
-  return hipErrorInvalidValue;
-}
-
-hipError_t detect_selftest_launch(int fm, int fn, int mm, int ncases,
-                                  const int* idesc, const float* fdesc,
-                                  float amp, float* out, hipStream_t stream) {
-  if (ncases < 1) return hipErrorInvalidValue;
-#define FT_SELFTEST_DETECT(FM_, FN_, MM_)                                   \
-  if (fm == FM_ && fn == FN_ && mm == MM_)                                  \
-    return launch_detect_selftest<FM_, FN_, MM_>(ncases, idesc, fdesc, amp, \
-                                                 out, stream);
-  FT_SELFTEST_DETECT(4, 2, 32)
-  FT_SELFTEST_DETECT(2, 1, 32)
-  FT_SELFTEST_DETECT(1, 2, 32)
-  FT_SELFTEST_DETECT(1, 1, 32)
-  FT_SELFTEST_DETECT(1, 1, 16)
-#undef FT_SELFTEST_DETECT
-  return hipErrorInvalidValue;
-}
-
-hipError_t locate_selftest_launch(int fm, int fn, int mm, int ncases,
-                                  const int* idesc, const float* fdesc,
-                                  float amp, float* out, hipStream_t stream) {
-  if (ncases < 1) return hipErrorInvalidValue;
-  // the wave-tile fragment shapes of the six tiers
-  if (fm == 4 && fn == 2 && mm == 32)
-    return launch_selftest<4, 2, 32>(ncases, idesc, fdesc, amp, out, stream);
-  if (fm == 2 && fn == 1 && mm == 32)
-    return launch_selftest<2, 1, 32>(ncases, idesc, fdesc, amp, out, stream);
-  if (fm == 1 && fn == 2 && mm == 32)
-    return launch_selftest<1, 2, 32>(ncases, idesc, fdesc, amp, out, stream);
-  if (fm == 1 && fn == 1 && mm == 32)
-    return launch_selftest<1, 1, 32>(ncases, idesc, fdesc, amp, out, stream);
-  if (fm == 1 && fn == 1 && mm == 16)
-    return launch_selftest<1, 1, 16>(ncases, idesc, fdesc, amp, out, stream);
+hipError_t selftest_launch(SelftestMode mode, const SelftestArgs& a) {
+  if (a.ncases < 1) return hipErrorInvalidValue;
+  switch (mode) {
+    case SELFTEST_LOCATE:
+      return launch_selftest<SELFTEST_LOCATE>(a);
+    case SELFTEST_REPORT:
+      if (a.capacity < 0 || !a.counters || (a.capacity > 0 && !a.events))
+        return hipErrorInvalidValue;
+      return launch_selftest<SELFTEST_REPORT>(a);
+    case SELFTEST_DETECT:
+      return launch_selftest<SELFTEST_DETECT>(a);
+  }
   return hipErrorInvalidValue;
 }
 

@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "ft_core.h"
 #include "ft_kernels.hpp"
 #include "ft_streamk.hpp"
 
@@ -48,18 +49,36 @@ size_t abft_workspace_floats_t(int M, int N, int K) {
   return 2 * (size_t)(M / WM) * abft_sstr(K);
 }
 
-// ABFT encode: precompute the plain + row-weighted segment checksums of A
-// (per WM-row band) into ws: one coalesced pass over the operand, ~1-2% of
-// the GEMM at N=4096 (vs -11.6% for the in-kernel cooperative sums pass
-// this replaces — tools/probe_ablate.hip).  Returns the row stride sstr
-// the fused kernel reads ws with.
+// The checksum operand of a fused kernel: SA and the row stride sstr it is
+// read with; both zero for a plain kernel.
+struct Checksums {
+  const float* SA = nullptr;
+  int sstr = 0;
+};
+
+// ABFT encode, when g.abft: precompute the plain + row-weighted segment
+// checksums of A (per WM-row band) into g.ws: one coalesced pass over the
+// operand, ~1-2% of the GEMM at N=4096 (vs -11.6% for the in-kernel
+// cooperative sums pass this replaces — tools/probe_ablate.hip).
 template <int WM>
-int abft_encode(int M, int K, const float* A, float* ws, hipStream_t stream) {
-  const int sstr = abft_sstr(K);
+hipError_t abft_encode(const GemmArgs& g, Checksums& cs) {
+  if (!g.abft) return hipSuccess;
+  if (!g.ws) return hipErrorInvalidValue;
+  cs.sstr = abft_sstr(g.K);
+  cs.SA = g.ws;
   RoctxRange rr("abft_encode_segsum");
-  hipLaunchKernelGGL((segsum_kernel<WM>), dim3(K), dim3(256), 0, stream, M,
-                     K, sstr, A, ws);
-  return sstr;
+  hipLaunchKernelGGL((segsum_kernel<WM>), dim3(g.K), dim3(256), 0, g.stream,
+                     g.M, g.K, cs.sstr, g.A, g.ws);
+  return hipSuccess;
+}
+
+// Inject+verify cadence: `steps` K-steps of a tile (classic: K / BK panels,
+// stream-K: 64-k units) in ~`windows` windows of whole steps (reference: 20
+// per GEMM, period K/20, ft_sgemm_huge.cuh:324-327).  Returns steps per
+// window.
+inline int window_stride(int steps, int windows) {
+  const int stride = steps / (windows > 0 ? windows : 20);
+  return stride < 1 ? 1 : stride;
 }
 
 // The fault log a launch runs with: the caller's when one is attached (fused
@@ -97,11 +116,9 @@ inline int device_cu_count() {
 // classic launch is preferable (heuristic) or the shape does not divide —
 // the caller then falls through to launch_tier.
 template <int BM, int BN, int BK, int BKF, int WM, int WN, int MM>
-hipError_t launch_tier_streamk_t(bool abft, bool inject, int M, int N, int K,
-                                 const float* A, const float* B, float* C,
-                                 float alpha, float beta, float tau,
-                                 float inj_mag, int verify_windows, float* ws,
-                                 hipStream_t stream, const FaultLog* log) {
+hipError_t launch_tier_streamk_t(const GemmArgs& g) {
+  const bool abft = g.abft, inject = g.inject;
+  const int M = g.M, N = g.N, K = g.K;
   const int mode = streamk_env_mode();
   if (mode == 0) return hipErrorNotSupported;
   if (M % BM || N % BN || K % 64 || K % (abft ? BKF : BK) || M % 4 ||
@@ -113,7 +130,7 @@ hipError_t launch_tier_streamk_t(bool abft, bool inject, int M, int N, int K,
   // grid G, always uses the unlogged kernel: attaching a log must not change
   // the decomposition (and so the summation order of C).  Nothing needs G
   // co-resident.
-  const FaultLog flog = attached_log(abft, log);
+  const FaultLog flog = attached_log(abft, g.log);
   const auto variant = [&](bool logged) {
     return select_variant(
         abft, inject, logged,
@@ -183,24 +200,16 @@ hipError_t launch_tier_streamk_t(bool abft, bool inject, int M, int N, int K,
   // different streams must not share it); hipMallocAsync is not legal
   // inside graph capture, so captured launches take the classic path.
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(stream, &cap);
+  (void)hipStreamIsCapturing(g.stream, &cap);
   if (cap != hipStreamCaptureStatusNone) return hipErrorNotSupported;
 
-  const float* SA = nullptr;
-  int sstr = 0;
-  if (abft) {
-    if (!ws) return hipErrorInvalidValue;
-    sstr = abft_encode<WM>(M, K, A, ws, stream);
-    SA = ws;
-  }
+  Checksums cs;
+  if (hipError_t e = abft_encode<WM>(g, cs); e != hipSuccess) return e;
   RoctxRange rr_main(abft ? (inject ? "ft_sgemm_streamk_abft_inject"
                                     : "ft_sgemm_streamk_abft")
                           : "sgemm_streamk_plain");
-  // inject+verify cadence: one pass per `istride` strip windows, targeting
-  // ~verify_windows groups per tile (reference: 20 per GEMM)
   const int upt = K >> 6;
-  int istride = upt / (verify_windows > 0 ? verify_windows : 20);
-  if (istride < 1) istride = 1;
+  const int istride = window_stride(upt, g.verify_windows);
 
   // split-tile partial slots: 2 per workgroup (head + tail partials).
   // One-time: raise the default mempool's release threshold so the pool
@@ -223,21 +232,21 @@ hipError_t launch_tier_streamk_t(bool abft, bool inject, int M, int N, int K,
   (void)pool_init;
   float* partials = nullptr;
   const size_t pbytes = (size_t)2 * G * BM * BN * sizeof(float);
-  if (hipMallocAsync((void**)&partials, pbytes, stream) != hipSuccess)
+  if (hipMallocAsync((void**)&partials, pbytes, g.stream) != hipSuccess)
     return hipErrorNotSupported;  // nothing mutated yet; classic path
 
-  hipLaunchKernelGGL(kfn_launch, dim3(G), dim3(THREADS), 0, stream, M, N, K, A,
-                     B, C, alpha, beta, istride, tau, inj_mag, SA, sstr,
-                     partials, flog);
+  hipLaunchKernelGGL(kfn_launch, dim3(G), dim3(THREADS), 0, g.stream, M, N, K,
+                     g.A, g.B, g.C, g.alpha, g.beta, istride, g.tau,
+                     g.inj_mag, cs.SA, cs.sstr, partials, flog);
   hipError_t err = hipGetLastError();
   if (err == hipSuccess) {
     // combine split tiles (fully-owned tiles exit immediately)
     hipLaunchKernelGGL((sk_fixup_kernel<BM, BN, WM, WN, MM>), dim3(tiles),
-                       dim3(THREADS), 0, stream, M, N, upt, G, alpha, beta,
-                       C, partials);
+                       dim3(THREADS), 0, g.stream, M, N, upt, G, g.alpha,
+                       g.beta, g.C, partials);
     err = hipGetLastError();
   }
-  (void)hipFreeAsync(partials, stream);
+  (void)hipFreeAsync(partials, g.stream);
   return err;
 }
 
@@ -245,33 +254,21 @@ hipError_t launch_tier_streamk_t(bool abft, bool inject, int M, int N, int K,
 // plain BK so the +1KB/wave checksum strips don't push the block over an
 // LDS-occupancy boundary — kernel_table.py bkf note).
 template <int BM, int BN, int BK, int BKF, int WM, int WN, int MM>
-hipError_t launch_tier(bool abft, bool inject, int M, int N, int K,
-                       const float* A, const float* B, float* C, float alpha,
-                       float beta, float tau, float inj_mag,
-                       int verify_windows, float* ws, hipStream_t stream,
-                       const FaultLog* log) {
+hipError_t launch_tier(const GemmArgs& g) {
+  const bool abft = g.abft, inject = g.inject;
+  const int M = g.M, N = g.N, K = g.K;
   const int bk_used = abft ? BKF : BK;
   if (M % BM || N % BN || K % bk_used || M % 4 || N % 4)
     return hipErrorInvalidValue;
   dim3 grid(M / BM, N / BN);
   dim3 block(tile_geom<BM, BN, BK, WM, WN, MM, false>::THREADS);
-  const int niter = K / bk_used;
-  // ~20 verify/inject windows per GEMM (reference period K/20,
-  // ft_sgemm_huge.cuh:324-327), whole BK panels; plain kernels run one
-  // burst.
-  int stride = abft ? niter / (verify_windows > 0 ? verify_windows : 20)
-                    : niter;
-  if (stride < 1) stride = 1;
-  const float* SA = nullptr;
-  int sstr = 0;
-  if (abft) {
-    if (!ws) return hipErrorInvalidValue;
-    sstr = abft_encode<WM>(M, K, A, ws, stream);
-    SA = ws;
-  }
+  // whole bk_used panels; a plain kernel runs them all in one burst
+  const int stride = window_stride(K / bk_used, abft ? g.verify_windows : 1);
+  Checksums cs;
+  if (hipError_t e = abft_encode<WM>(g, cs); e != hipSuccess) return e;
   RoctxRange rr_main(abft ? (inject ? "ft_sgemm_abft_inject" : "ft_sgemm_abft")
                           : "sgemm_plain");
-  const FaultLog flog = attached_log(abft, log);
+  const FaultLog flog = attached_log(abft, g.log);
   const auto kfn = select_variant(
       abft, inject, flog.counters != nullptr,
       &sgemm_mfma<BM, BN, BK, WM, WN, MM, false, false>,
@@ -279,8 +276,9 @@ hipError_t launch_tier(bool abft, bool inject, int M, int N, int K,
         return &sgemm_mfma<BM, BN, BKF, WM, WN, MM, true, decltype(inj)::value,
                            2, decltype(lg)::value>;
       });
-  hipLaunchKernelGGL(kfn, grid, block, 0, stream, M, N, K, A, B, C, alpha,
-                     beta, stride, stride, tau, inj_mag, SA, sstr, flog);
+  hipLaunchKernelGGL(kfn, grid, block, 0, g.stream, M, N, K, g.A, g.B, g.C,
+                     g.alpha, g.beta, stride, stride, g.tau, g.inj_mag, cs.SA,
+                     cs.sstr, flog);
   return hipGetLastError();
 }
 

@@ -67,21 +67,21 @@ void sgemm(int64_t tier, bool abft, bool inject, at::Tensor a, at::Tensor b,
               "ft_sgemm: tier ", tier, " requires M,N,K multiples of its "
               "tile (M=", M, " N=", N, " K=", K, ")");
   auto stream = at::cuda::getCurrentCUDAStream();
+  ftsgemm::GemmArgs g{abft, inject, (int)M, (int)N, (int)K,
+                      a.const_data_ptr<float>(), b.const_data_ptr<float>(),
+                      c.mutable_data_ptr<float>(), (float)alpha, (float)beta,
+                      (float)tau, (float)inj_mag, (int)verify_windows};
+  g.stream = stream.stream();
+  g.log = flog.counters ? &flog : nullptr;
   at::Tensor ws;
-  float* ws_ptr = nullptr;
   if (abft) {
-    // segment-checksum scratch (SA/SB), via the caching allocator
+    // segment-checksum scratch (SA), via the caching allocator
     size_t n = ftsgemm::sgemm_abft_workspace_floats((int)tier, (int)M,
                                                     (int)N, (int)K);
     ws = at::empty({(int64_t)n}, a.options());
-    ws_ptr = ws.mutable_data_ptr<float>();
+    g.ws = ws.mutable_data_ptr<float>();
   }
-  hipError_t err = ftsgemm::sgemm_tier_launch(
-      (int)tier, abft, inject, (int)M, (int)N, (int)K,
-      a.const_data_ptr<float>(), b.const_data_ptr<float>(),
-      c.mutable_data_ptr<float>(), (float)alpha, (float)beta, (float)tau,
-      (float)inj_mag, (int)verify_windows, ws_ptr, stream.stream(),
-      flog.counters ? &flog : nullptr);
+  hipError_t err = ftsgemm::sgemm_tier_launch((int)tier, g);
   TORCH_CHECK(err == hipSuccess,
               "ft_sgemm launch failed: ", hipGetErrorString(err));
 }
@@ -132,32 +132,59 @@ bool tier_supported(int64_t tier, int64_t M, int64_t N, int64_t K) {
   return ftsgemm::sgemm_tier_supported((int)tier, (int)M, (int)N, (int)K);
 }
 
-// idesc: (ncases, 9) int32, fdesc: (ncases, 3) fp32 — see ft_core.h.
-// Returns the (3, ncases, fm*fn*nreg, 64) {shipped, reference, clean} tiles.
-at::Tensor locate_selftest(int64_t fm, int64_t fn, int64_t mm,
-                           at::Tensor idesc, at::Tensor fdesc, double amp) {
-  TORCH_CHECK(idesc.is_cuda() && fdesc.is_cuda(),
-              "locate_selftest: descriptors must be on a GPU device");
+// idesc (ncases, 9) int32 and fdesc (ncases, 3) fp32, both on a GPU — see
+// ft_core.h.  Returns ncases.
+int64_t check_selftest_descs(const char* name, const at::Tensor& idesc,
+                             const at::Tensor& fdesc) {
+  TORCH_CHECK(idesc.is_cuda() && fdesc.is_cuda(), name,
+              ": descriptors must be on a GPU device");
   TORCH_CHECK(idesc.scalar_type() == at::kInt && idesc.is_contiguous() &&
                   idesc.dim() == 2 && idesc.size(1) == 9,
-              "locate_selftest: idesc must be contiguous int32 (ncases, 9)");
+              name, ": idesc must be contiguous int32 (ncases, 9)");
   const int64_t ncases = idesc.size(0);
   TORCH_CHECK(fdesc.scalar_type() == at::kFloat && fdesc.is_contiguous() &&
                   fdesc.dim() == 2 && fdesc.size(0) == ncases &&
                   fdesc.size(1) == 3,
-              "locate_selftest: fdesc must be contiguous fp32 (ncases, 3)");
-  TORCH_CHECK(ncases >= 1 && ncases <= (1 << 20),
-              "locate_selftest: 1..2^20 cases");
-  const int64_t nreg = mm == 32 ? 16 : 4;
-  at::Tensor out = at::empty({3, ncases, fm * fn * nreg, 64},
+              name, ": fdesc must be contiguous fp32 (ncases, 3)");
+  TORCH_CHECK(ncases >= 1 && ncases <= (1 << 20), name, ": 1..2^20 cases");
+  return ncases;
+}
+
+// Checked launch arguments of a self-test entry, `out` still unset.  The
+// fragment shape is range-checked here because the entries size their outputs
+// from it; a shape in range that no tier has is rejected by the launch.
+ftsgemm::SelftestArgs selftest_args(const char* name, int64_t fm, int64_t fn,
+                                    int64_t mm, const at::Tensor& idesc,
+                                    const at::Tensor& fdesc, double amp) {
+  const int64_t ncases = check_selftest_descs(name, idesc, fdesc);
+  TORCH_CHECK(fm >= 1 && fm <= 4 && fn >= 1 && fn <= 2 &&
+                  (mm == 32 || mm == 16),
+              name, ": unsupported (fm, fn, mm)");
+  ftsgemm::SelftestArgs a{(int)fm, (int)fn, (int)mm, (int)ncases,
+                          idesc.const_data_ptr<int>(),
+                          fdesc.const_data_ptr<float>(), (float)amp};
+  a.stream = at::cuda::getCurrentCUDAStream().stream();
+  return a;
+}
+
+// accumulators per lane of an mm-wide MFMA fragment
+int64_t nreg(int64_t mm) { return mm == 32 ? 16 : 4; }
+
+void launch_selftest(const char* name, ftsgemm::SelftestMode mode,
+                     ftsgemm::SelftestArgs& a, at::Tensor& out) {
+  a.out = out.mutable_data_ptr<float>();
+  hipError_t err = ftsgemm::selftest_launch(mode, a);
+  TORCH_CHECK(err == hipSuccess, name, ": unsupported (fm, fn, mm) or launch "
+              "failure: ", hipGetErrorString(err));
+}
+
+// Returns the (3, ncases, fm*fn*nreg, 64) {shipped, reference, clean} tiles.
+at::Tensor locate_selftest(int64_t fm, int64_t fn, int64_t mm,
+                           at::Tensor idesc, at::Tensor fdesc, double amp) {
+  auto a = selftest_args("locate_selftest", fm, fn, mm, idesc, fdesc, amp);
+  at::Tensor out = at::empty({3, a.ncases, fm * fn * nreg(mm), 64},
                              fdesc.options());
-  auto stream = at::cuda::getCurrentCUDAStream();
-  hipError_t err = ftsgemm::locate_selftest_launch(
-      (int)fm, (int)fn, (int)mm, (int)ncases, idesc.const_data_ptr<int>(),
-      fdesc.const_data_ptr<float>(), (float)amp,
-      out.mutable_data_ptr<float>(), stream.stream());
-  TORCH_CHECK(err == hipSuccess, "locate_selftest: unsupported (fm, fn, mm) ",
-              "or launch failure: ", hipGetErrorString(err));
+  launch_selftest("locate_selftest", ftsgemm::SELFTEST_LOCATE, a, out);
   return out;
 }
 
@@ -165,31 +192,10 @@ at::Tensor locate_selftest(int64_t fm, int64_t fn, int64_t mm,
 // wave residual, per fn the lane partial p[fn], per fn the screen's verdict.
 at::Tensor detect_selftest(int64_t fm, int64_t fn, int64_t mm,
                            at::Tensor idesc, at::Tensor fdesc, double amp) {
-  TORCH_CHECK(idesc.is_cuda() && fdesc.is_cuda(),
-              "detect_selftest: descriptors must be on a GPU device");
-  TORCH_CHECK(idesc.scalar_type() == at::kInt && idesc.is_contiguous() &&
-                  idesc.dim() == 2 && idesc.size(1) == 9,
-              "detect_selftest: idesc must be contiguous int32 (ncases, 9)");
-  const int64_t ncases = idesc.size(0);
-  TORCH_CHECK(fdesc.scalar_type() == at::kFloat && fdesc.is_contiguous() &&
-                  fdesc.dim() == 2 && fdesc.size(0) == ncases &&
-                  fdesc.size(1) == 3,
-              "detect_selftest: fdesc must be contiguous fp32 (ncases, 3)");
-  TORCH_CHECK(ncases >= 1 && ncases <= (1 << 20),
-              "detect_selftest: 1..2^20 cases");
-  TORCH_CHECK(fm >= 1 && fm <= 4 && fn >= 1 && fn <= 2 &&
-                  (mm == 32 || mm == 16),
-              "detect_selftest: unsupported (fm, fn, mm)");
-  const int64_t nreg = mm == 32 ? 16 : 4;
-  at::Tensor out = at::empty({ncases, fm * fn * nreg + 1 + 2 * fn, 64},
-                             fdesc.options());
-  auto stream = at::cuda::getCurrentCUDAStream();
-  hipError_t err = ftsgemm::detect_selftest_launch(
-      (int)fm, (int)fn, (int)mm, (int)ncases, idesc.const_data_ptr<int>(),
-      fdesc.const_data_ptr<float>(), (float)amp,
-      out.mutable_data_ptr<float>(), stream.stream());
-  TORCH_CHECK(err == hipSuccess, "detect_selftest: unsupported (fm, fn, mm) ",
-              "or launch failure: ", hipGetErrorString(err));
+  auto a = selftest_args("detect_selftest", fm, fn, mm, idesc, fdesc, amp);
+  at::Tensor out = at::empty(
+      {a.ncases, fm * fn * nreg(mm) + 1 + 2 * fn, 64}, fdesc.options());
+  launch_selftest("detect_selftest", ftsgemm::SELFTEST_DETECT, a, out);
   return out;
 }
 
@@ -198,37 +204,19 @@ at::Tensor detect_selftest(int64_t fm, int64_t fn, int64_t mm,
 std::tuple<at::Tensor, at::Tensor, at::Tensor> locate_selftest_report(
     int64_t fm, int64_t fn, int64_t mm, at::Tensor idesc, at::Tensor fdesc,
     double amp, int64_t capacity) {
-  TORCH_CHECK(idesc.is_cuda() && fdesc.is_cuda(),
-              "locate_selftest_report: descriptors must be on a GPU device");
-  TORCH_CHECK(idesc.scalar_type() == at::kInt && idesc.is_contiguous() &&
-                  idesc.dim() == 2 && idesc.size(1) == 9,
-              "locate_selftest_report: idesc must be contiguous int32 "
-              "(ncases, 9)");
-  const int64_t ncases = idesc.size(0);
-  TORCH_CHECK(fdesc.scalar_type() == at::kFloat && fdesc.is_contiguous() &&
-                  fdesc.dim() == 2 && fdesc.size(0) == ncases &&
-                  fdesc.size(1) == 3,
-              "locate_selftest_report: fdesc must be contiguous fp32 "
-              "(ncases, 3)");
-  TORCH_CHECK(ncases >= 1 && ncases <= (1 << 20),
-              "locate_selftest_report: 1..2^20 cases");
-  TORCH_CHECK(capacity >= 1 && capacity <= 1024,
-              "locate_selftest_report: capacity 1..1024");
-  const int64_t nreg = mm == 32 ? 16 : 4;
-  at::Tensor out = at::empty({ncases, fm * fn * nreg, 64}, fdesc.options());
+  const char* name = "locate_selftest_report";
+  auto a = selftest_args(name, fm, fn, mm, idesc, fdesc, amp);
+  TORCH_CHECK(capacity >= 1 && capacity <= 1024, name, ": capacity 1..1024");
+  at::Tensor out = at::empty({a.ncases, fm * fn * nreg(mm), 64},
+                             fdesc.options());
   at::Tensor counters =
-      at::zeros({ncases, ftsgemm::FLOG_N_COUNTERS}, idesc.options());
+      at::zeros({a.ncases, ftsgemm::FLOG_N_COUNTERS}, idesc.options());
   at::Tensor events = at::zeros(
-      {ncases, capacity, ftsgemm::FLOG_EVENT_DWORDS}, idesc.options());
-  auto stream = at::cuda::getCurrentCUDAStream();
-  hipError_t err = ftsgemm::locate_selftest_report_launch(
-      (int)fm, (int)fn, (int)mm, (int)ncases, idesc.const_data_ptr<int>(),
-      fdesc.const_data_ptr<float>(), (float)amp,
-      out.mutable_data_ptr<float>(), counters.mutable_data_ptr<int>(),
-      events.mutable_data_ptr<int>(), (int)capacity, stream.stream());
-  TORCH_CHECK(err == hipSuccess,
-              "locate_selftest_report: unsupported (fm, fn, mm) or launch "
-              "failure: ", hipGetErrorString(err));
+      {a.ncases, capacity, ftsgemm::FLOG_EVENT_DWORDS}, idesc.options());
+  a.counters = counters.mutable_data_ptr<int>();
+  a.events = events.mutable_data_ptr<int>();
+  a.capacity = (int)capacity;
+  launch_selftest(name, ftsgemm::SELFTEST_REPORT, a, out);
   return {out, counters, events};
 }
 

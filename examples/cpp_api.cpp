@@ -26,10 +26,10 @@ int main() {
   // fused-ABFT huge tier with the 20-fault self-test
   size_t wsf = ftsgemm::sgemm_abft_workspace_floats(FT_TIER_ID_huge, n, n, n);
   hipMalloc(&ws, wsf * sizeof(float));
-  hipError_t err = ftsgemm::sgemm_tier_launch(
-      FT_TIER_ID_huge, /*abft=*/true, /*inject=*/true, n, n, n, dA, dB, dC,
-      /*alpha=*/1.f, /*beta=*/0.f, /*tau=*/9500.f, /*inj_mag=*/10000.f,
-      /*verify_windows=*/20, ws, /*stream=*/0);
+  ftsgemm::GemmArgs g{/*abft=*/true, /*inject=*/true, n, n, n, dA, dB, dC,
+                      /*alpha=*/1.f, /*beta=*/0.f, /*tau=*/9500.f,
+                      /*inj_mag=*/10000.f, /*verify_windows=*/20, ws};
+  hipError_t err = ftsgemm::sgemm_tier_launch(FT_TIER_ID_huge, g);
   if (err != hipSuccess) {
     fprintf(stderr, "launch failed: %s\n", hipGetErrorString(err));
     return 1;

@@ -8,6 +8,7 @@ implementation and the extension is not required.
 
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from ..kernel_table import (ERR_BOUND, ERROR_INJECT, KERNEL_TABLE, TIERS)
@@ -86,6 +87,25 @@ def baseline_ft(a, b, c, alpha: float = 1.0, beta: float = 0.0,
     """Kernel id 10: non-fused rocBLAS ABFT chain.  Returns (c, verdicts)."""
     res = _require_ext().baseline_ft(a, b, c, alpha, beta, panel_k)
     return c, res
+
+
+def selftest_descriptors(rows):
+    """Pack self-test cases into the (idesc, fdesc) arrays the three
+    self-test entries take.  rows: a list of (faults, tau), faults a list of
+    at most two (fm, fn, reg, lane, mag).  Returns CPU numpy arrays: idesc
+    (ncases, 9) int32 = {nfault, (fm, fn, reg, lane) x 2} and fdesc
+    (ncases, 3) float32 = {mag0, mag1, tau}, unused slots zero."""
+    idesc = np.zeros((len(rows), 9), dtype=np.int32)
+    fdesc = np.zeros((len(rows), 3), dtype=np.float32)
+    for i, (faults, tau) in enumerate(rows):
+        if len(faults) > 2:
+            raise ValueError(f"case {i}: {len(faults)} faults, at most 2")
+        idesc[i, 0] = len(faults)
+        for f, (fm, fn, reg, lane, mag) in enumerate(faults):
+            idesc[i, 1 + 4 * f:5 + 4 * f] = (fm, fn, reg, lane)
+            fdesc[i, f] = mag
+        fdesc[i, 2] = tau
+    return idesc, fdesc
 
 
 def locate_selftest_report(fm: int, fn: int, mm: int, idesc: torch.Tensor,

@@ -122,9 +122,9 @@ def predict_injected_events(tier: str, m: int, n: int, k: int,
     """The exact events the classic fused kernel's injector must produce for
     an (m, n, k) GEMM on `tier`, sorted by (i, j, k_begin).
 
-    Derived from csrc/tier_launch.hpp (launch_tier: window stride) and
-    csrc/ft_kernels.hpp (sgemm_mfma: victim rotation, MFMA accumulator
-    layout): every block injects once per verify window w into
+    Derived from csrc/tier_launch.hpp (window_stride as launch_tier calls
+    it) and csrc/ft_kernels.hpp (sgemm_mfma: victim rotation, MFMA
+    accumulator layout): every block injects once per verify window w into
     acc[0][0][0] of thread (w * 67) % THREADS.
     """
     t = TILING[tier]

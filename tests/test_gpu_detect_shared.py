@@ -56,12 +56,9 @@ def _cases(fm_n, fn_n):
              for f in (1.05, 0.95) for fm in range(fm_n)
              for fn in range(fn_n) for reg in (0, NREG - 1)
              for lane in (0, 31, 32, 63)]
-    idesc = np.zeros((len(sites), 9), dtype=np.int32)
-    fdesc = np.zeros((len(sites), 3), dtype=np.float32)
-    for i, (f, fm, fn, reg, lane) in enumerate(sites):
-        idesc[i, :5] = (1, fm, fn, reg, lane)
-        fdesc[i, 0] = f * TAU
-        fdesc[i, 2] = TAU
+    idesc, fdesc = ops.selftest_descriptors(
+        [([(fm, fn, reg, lane, f * TAU)], TAU)
+         for f, fm, fn, reg, lane in sites])
     return sites, idesc, fdesc
 
 

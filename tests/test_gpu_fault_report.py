@@ -17,7 +17,6 @@ for |rc - ERROR_INJECT| here.
 
 import os
 
-import numpy as np
 import pytest
 import torch
 
@@ -211,14 +210,7 @@ def _acc_row(reg, sub):
 
 
 def _descs(rows):
-    idesc = np.zeros((len(rows), 9), dtype=np.int32)
-    fdesc = np.zeros((len(rows), 3), dtype=np.float32)
-    for i, (faults, tau) in enumerate(rows):
-        idesc[i, 0] = len(faults)
-        for f, (fm, fn, reg, lane, mag) in enumerate(faults):
-            idesc[i, 1 + 4 * f:5 + 4 * f] = (fm, fn, reg, lane)
-            fdesc[i, f] = mag
-        fdesc[i, 2] = tau
+    idesc, fdesc = ops.selftest_descriptors(rows)
     return torch.from_numpy(idesc).cuda(), torch.from_numpy(fdesc).cuda()
 
 

@@ -77,14 +77,7 @@ def _cases(fm_n, fn_n, mm):
         False)
     add("tau100_mag200", [(fm_n - 1, fn_n - 1, 2, 50, 200.0)], 100.0, True)
 
-    idesc = np.zeros((len(rows), 9), dtype=np.int32)
-    fdesc = np.zeros((len(rows), 3), dtype=np.float32)
-    for i, (faults, tau, _) in enumerate(rows):
-        idesc[i, 0] = len(faults)
-        for f, (fm, fn, reg, lane, mag) in enumerate(faults):
-            idesc[i, 1 + 4 * f:5 + 4 * f] = (fm, fn, reg, lane)
-            fdesc[i, f] = mag
-        fdesc[i, 2] = tau
+    idesc, fdesc = ops.selftest_descriptors([r[:2] for r in rows])
     ok = np.array([r[2] for r in rows])
     return idesc, fdesc, ok, special
 

@@ -173,3 +173,26 @@ def test_streamk_partition_properties():
                 assert head_writers[gc][0] == t
                 units += head_writers[gc][1]
             assert units == upt, f"tile {t}: {units} != {upt}"
+
+
+def test_selftest_descriptors_packing():
+    import pytest
+
+    from ft_sgemm_amd import ops
+
+    idesc, fdesc = ops.selftest_descriptors([
+        ([(3, 1, 15, 45, 10000.0), (0, 1, 2, 63, -1.5)], 9500.0),
+        ([], 100.0),
+        ([(1, 0, 7, 9, 200.0)], 100.0),
+    ])
+    assert idesc.dtype == np.int32 and idesc.shape == (3, 9)
+    assert fdesc.dtype == np.float32 and fdesc.shape == (3, 3)
+    # {nfault, (fm, fn, reg, lane) x 2} / {mag0, mag1, tau}
+    assert idesc[0].tolist() == [2, 3, 1, 15, 45, 0, 1, 2, 63]
+    assert fdesc[0].tolist() == [10000.0, -1.5, 9500.0]
+    assert idesc[1].tolist() == [0] * 9  # nfault == 0
+    assert fdesc[1].tolist() == [0.0, 0.0, 100.0]
+    assert idesc[2].tolist() == [1, 1, 0, 7, 9, 0, 0, 0, 0]
+    assert fdesc[2].tolist() == [200.0, 0.0, 100.0]
+    with pytest.raises(ValueError):
+        ops.selftest_descriptors([([(0, 0, 0, 0, 1.0)] * 3, 1.0)])
