@@ -11,8 +11,9 @@
 
 namespace ftsgemm {
 
-#define FT_DECL(name, BM, BN, BK, WM, WN, MM)      \
-  hipError_t launch_tier_##name(const GemmArgs& g); \
+#define FT_DECL(name, BM, BN, BK, WM, WN, MM)              \
+  hipError_t launch_tier_##name(const GemmArgs& g);         \
+  hipError_t launch_tier_batched_##name(const GemmArgs& g); \
   size_t abft_ws_floats_##name(int M, int N, int K);
 FT_TIER_LIST(FT_DECL)
 #undef FT_DECL
@@ -23,12 +24,14 @@ namespace {
 // FT_TIER_ID_<name> by position in that list, so a tier id indexes the table.
 struct TierRow {
   hipError_t (*launch)(const GemmArgs&);
+  hipError_t (*launch_batched)(const GemmArgs&);  // batch > 1
   size_t (*ws_floats)(int, int, int);
   int bm, bn, bk;
 };
 const TierRow kTiers[FT_N_TIERS] = {
-#define FT_ROW(name, BM, BN, BK, WM, WN, MM) \
-  {launch_tier_##name, abft_ws_floats_##name, BM, BN, BK},
+#define FT_ROW(name, BM, BN, BK, WM, WN, MM)                             \
+  {launch_tier_##name, launch_tier_batched_##name, abft_ws_floats_##name, \
+   BM, BN, BK},
     FT_TIER_LIST(FT_ROW)
 #undef FT_ROW
 };
@@ -41,7 +44,8 @@ const TierRow* tier_row(int tier) {
 
 hipError_t sgemm_tier_launch(int tier, const GemmArgs& g) {
   const TierRow* t = tier_row(tier);
-  return t ? t->launch(g) : hipErrorInvalidValue;
+  if (!t || g.batch < 1) return hipErrorInvalidValue;
+  return g.batch > 1 ? t->launch_batched(g) : t->launch(g);
 }
 
 // Workspace floats needed by the fused-ABFT path of a tier (the segment-sum
@@ -49,6 +53,11 @@ hipError_t sgemm_tier_launch(int tier, const GemmArgs& g) {
 size_t sgemm_abft_workspace_floats(int tier, int M, int N, int K) {
   const TierRow* t = tier_row(tier);
   return t ? t->ws_floats(M, N, K) : 0;
+}
+
+size_t sgemm_abft_workspace_floats_batched(int tier, int M, int N, int K,
+                                           int nA) {
+  return (nA > 0 ? (size_t)nA : 0) * sgemm_abft_workspace_floats(tier, M, N, K);
 }
 
 bool sgemm_tier_supported(int tier, int M, int N, int K) {

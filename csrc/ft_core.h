@@ -19,6 +19,19 @@ namespace ftsgemm {
 // appends one event per detected fault.  The launch neither zeroes,
 // allocates nor syncs for it — counts accumulate until the caller clears
 // them — and with log == nullptr the kernels write nothing.
+//
+// batch > 1 is a strided batch: for b in [0, batch), C_b = alpha * A_b *
+// B_b^T + beta * C_b with X_b = X + b * strideX, strides in floats.  strideA
+// and strideB may be 0 (one operand shared by every entry); strideC must be
+// >= M*N; every stride must be a multiple of 4 floats and A, B, C and ws
+// 16-byte aligned; batch <= 65535.  ws then holds
+// sgemm_abft_workspace_floats_batched(tier, M, N, K, nA) floats, nA = 1 for
+// a shared A (strideA == 0) and batch otherwise, and `log` points at the
+// first of `batch` logs laid out as counters[batch][FLOG_N_COUNTERS] and
+// events[batch][capacity][FLOG_EVENT_DWORDS]: entry b reports into log b.
+// A batched launch always takes the classic tile-per-workgroup path
+// (FT_SGEMM_STREAMK has no effect on it); batch == 1 is today's launch and
+// ignores the strides.
 struct GemmArgs {
   bool abft, inject;
   int M, N, K;
@@ -29,6 +42,8 @@ struct GemmArgs {
   float* ws = nullptr;
   hipStream_t stream = 0;
   const FaultLog* log = nullptr;
+  int batch = 1;
+  long long strideA = 0, strideB = 0, strideC = 0;
 };
 
 // Launch tier `tier` (id per generated/tile_params.h).
@@ -37,6 +52,10 @@ hipError_t sgemm_tier_launch(int tier, const GemmArgs& g);
 bool sgemm_tier_supported(int tier, int M, int N, int K);
 
 size_t sgemm_abft_workspace_floats(int tier, int M, int N, int K);
+
+// nA consecutive copies of the per-matrix workspace (GemmArgs note).
+size_t sgemm_abft_workspace_floats_batched(int tier, int M, int N, int K,
+                                           int nA);
 
 // Device self-test of the fused kernels' shared detect / locate / correct
 // (locate_selftest.hip): one single-wave block per case plants up to two

@@ -394,9 +394,8 @@ __device__ __attribute__((always_inline)) inline void locate_correct(
 // fused kernel streams 64-k strips with 4-B/lane global_load_lds pairs,
 // never crossing rows).
 template <int SEG>
-__global__ __launch_bounds__(256) void segsum_kernel(
-    int M, int K, int sstr, const float* __restrict__ A,
-    float* __restrict__ S) {
+__device__ __attribute__((always_inline)) inline void segsum_column(
+    int M, int sstr, const float* __restrict__ A, float* __restrict__ S) {
   const int k = blockIdx.x;
   const int tid = threadIdx.x;
   const float* col = A + (size_t)k * M;
@@ -421,6 +420,24 @@ __global__ __launch_bounds__(256) void segsum_kernel(
       S[(size_t)(idx / SEG) * 2 * sstr + 2 * k + 1] = w;
     }
   }
+}
+
+template <int SEG>
+__global__ __launch_bounds__(256) void segsum_kernel(
+    int M, int K, int sstr, const float* __restrict__ A,
+    float* __restrict__ S) {
+  segsum_column<SEG>(M, sstr, A, S);
+}
+
+// Strided-batched twin, launched on a (K, nA) grid: blockIdx.y picks the
+// matrix (strideA floats apart) and its copy of the per-matrix workspace
+// layout (strideS floats apart).
+template <int SEG>
+__global__ __launch_bounds__(256) void segsum_batched_kernel(
+    int M, int K, int sstr, const float* __restrict__ A,
+    float* __restrict__ S, long long strideA, long long strideS) {
+  const long long z = blockIdx.y;
+  segsum_column<SEG>(M, sstr, A + z * strideA, S + z * strideS);
 }
 
 // ---------------------------------------------------------------------------
@@ -578,15 +595,39 @@ __device__ __attribute__((always_inline)) inline void verify_window(
   }
 }
 
+// Strides of a strided-batched launch, in floats: entry z of the batch reads
+// A + z * A, B + z * B and SA + z * SA and writes C + z * C.  A stride of 0
+// shares one operand (and its segment sums) between all entries.
+struct BatchStrides {
+  long long A = 0, B = 0, C = 0, SA = 0;
+};
+
+// BATCHED: one GEMM per blockIdx.z (launch_tier_batched).  Only the prologue
+// knows: it moves the operand pointers, and the fault log to the entry's own
+// (counters[z], events[z]) of a batch-major log array, by wave-uniform 64-bit
+// offsets.  Everything below it is the single-matrix kernel, so an entry's C
+// has the bits of a single launch on the same operands.  The unbatched
+// instantiations never look at bs.
 template <int BM, int BN, int BK, int WM, int WN, int MM, bool ABFT,
-          bool INJECT, int OCC = 2, bool LOG = false>
+          bool INJECT, int OCC = 2, bool LOG = false, bool BATCHED = false>
 __global__ __launch_bounds__(
     (tile_geom<BM, BN, BK, WM, WN, MM, ABFT>::THREADS), OCC) void sgemm_mfma(
     int M, int N, int K, const float* __restrict__ A,
     const float* __restrict__ B, float* __restrict__ C, float alpha,
     float beta, int verify_iters, int inject_stride, float tau, float inj_mag,
-    const float* __restrict__ SA, int sstr, FaultLog flog) {
+    const float* __restrict__ SA, int sstr, FaultLog flog, BatchStrides bs) {
   using G = tile_geom<BM, BN, BK, WM, WN, MM, ABFT>;
+  if constexpr (BATCHED) {
+    const long long z = blockIdx.z;
+    A += z * bs.A;
+    B += z * bs.B;
+    C += z * bs.C;
+    if constexpr (ABFT) SA += z * bs.SA;
+    if constexpr (LOG) {
+      flog.counters += z * FLOG_N_COUNTERS;
+      flog.events += z * flog.capacity * FLOG_EVENT_DWORDS;
+    }
+  }
   using T = typename G::T;
   constexpr int KSTEP = G::KSTEP, THREADS = G::THREADS, FM = G::FM,
                 FN = G::FN, BUF = G::BUF, STRIP_OFF = G::STRIP_OFF,

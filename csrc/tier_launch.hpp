@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <roctracer/roctx.h>
 
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
@@ -278,7 +279,65 @@ hipError_t launch_tier(const GemmArgs& g) {
       });
   hipLaunchKernelGGL(kfn, grid, block, 0, g.stream, M, N, K, g.A, g.B, g.C,
                      g.alpha, g.beta, stride, stride, g.tau, g.inj_mag, cs.SA,
-                     cs.sstr, flog);
+                     cs.sstr, flog, BatchStrides{});
+  return hipGetLastError();
+}
+
+// Strided-batched launch of one tier: g.batch GEMMs on a (M/BM, N/BN, batch)
+// grid of the classic kernel's BATCHED twin, entry b on A + b*strideA,
+// B + b*strideB, C + b*strideC.  strideA == 0 shares A: its segment sums are
+// then encoded once and read by every entry; otherwise g.ws holds one copy of
+// the per-matrix workspace layout per entry.  With a log attached, g.log is
+// the first of g.batch logs (ft_core.h).  Always the classic decomposition:
+// there is no batched stream-K, and FT_SGEMM_STREAMK is not consulted.  No
+// allocation and no sync, so the launch can be captured.
+template <int BM, int BN, int BK, int BKF, int WM, int WN, int MM>
+hipError_t launch_tier_batched(const GemmArgs& g) {
+  const bool abft = g.abft, inject = g.inject;
+  const int M = g.M, N = g.N, K = g.K;
+  const int bk_used = abft ? BKF : BK;
+  if (M % BM || N % BN || K % bk_used || M % 4 || N % 4)
+    return hipErrorInvalidValue;
+  // blockIdx.z carries the entry; 16-B staging and the f32x4 epilogue need
+  // every entry's base 16-B aligned
+  if (g.batch < 1 || g.batch > 65535) return hipErrorInvalidValue;
+  if (g.strideA < 0 || g.strideB < 0 || g.strideA % 4 || g.strideB % 4 ||
+      g.strideC % 4 || g.strideC < (long long)M * N)
+    return hipErrorInvalidValue;
+  if (((uintptr_t)g.A | (uintptr_t)g.B | (uintptr_t)g.C | (uintptr_t)g.ws) &
+      15)
+    return hipErrorInvalidValue;
+  dim3 grid(M / BM, N / BN, g.batch);
+  dim3 block(tile_geom<BM, BN, BK, WM, WN, MM, false>::THREADS);
+  const int stride = window_stride(K / bk_used, abft ? g.verify_windows : 1);
+  BatchStrides bs{g.strideA, g.strideB, g.strideC, 0};
+  Checksums cs;
+  if (abft) {
+    if (!g.ws) return hipErrorInvalidValue;
+    const int nA = g.strideA == 0 ? 1 : g.batch;
+    const long long ws_each =
+        (long long)abft_workspace_floats_t<WM, WN>(M, N, K);
+    bs.SA = nA == 1 ? 0 : ws_each;
+    cs.sstr = abft_sstr(K);
+    cs.SA = g.ws;
+    RoctxRange rr("abft_encode_segsum_batched");
+    hipLaunchKernelGGL((segsum_batched_kernel<WM>), dim3(K, nA), dim3(256), 0,
+                       g.stream, M, K, cs.sstr, g.A, g.ws, g.strideA, ws_each);
+  }
+  RoctxRange rr_main(abft ? (inject ? "ft_sgemm_batched_abft_inject"
+                                    : "ft_sgemm_batched_abft")
+                          : "sgemm_batched_plain");
+  const FaultLog flog = attached_log(abft, g.log);
+  const auto kfn = select_variant(
+      abft, inject, flog.counters != nullptr,
+      &sgemm_mfma<BM, BN, BK, WM, WN, MM, false, false, 2, false, true>,
+      [](auto inj, auto lg) {
+        return &sgemm_mfma<BM, BN, BKF, WM, WN, MM, true, decltype(inj)::value,
+                           2, decltype(lg)::value, true>;
+      });
+  hipLaunchKernelGGL(kfn, grid, block, 0, g.stream, M, N, K, g.A, g.B, g.C,
+                     g.alpha, g.beta, stride, stride, g.tau, g.inj_mag, cs.SA,
+                     cs.sstr, flog, bs);
   return hipGetLastError();
 }
 

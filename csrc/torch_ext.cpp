@@ -86,6 +86,124 @@ void sgemm(int64_t tier, bool abft, bool inject, at::Tensor a, at::Tensor b,
               "ft_sgemm launch failed: ", hipGetErrorString(err));
 }
 
+// Layout of a strided-batched call (mirrors ops.batched_layout, the Python
+// helper that raises ValueError before a call gets here): a (B,K,M),
+// b (B,K,N), c (B,N,M), inner two dimensions contiguous, the batch stride
+// read from the tensor.
+struct BatchedLayout {
+  int64_t batch, M, N, K, sA, sB, sC;
+};
+
+BatchedLayout check_batched_inputs(const at::Tensor& a, const at::Tensor& b,
+                                   const at::Tensor& c) {
+  const char* nm = "ft_sgemm_batched";
+  TORCH_CHECK(a.is_cuda() && b.is_cuda() && c.is_cuda(), nm,
+              ": tensors must be on a GPU device");
+  TORCH_CHECK(a.device() == b.device() && a.device() == c.device(), nm,
+              ": tensors must be on one device");
+  TORCH_CHECK(a.scalar_type() == at::kFloat &&
+                  b.scalar_type() == at::kFloat &&
+                  c.scalar_type() == at::kFloat,
+              nm, ": fp32 only (SGEMM)");
+  TORCH_CHECK(a.dim() == 3 && b.dim() == 3 && c.dim() == 3, nm,
+              ": 3-D tensors a (B,K,M), b (B,K,N), c (B,N,M) expected");
+  BatchedLayout L{c.size(0), a.size(2), b.size(2), a.size(1),
+                  a.stride(0), b.stride(0), c.stride(0)};
+  TORCH_CHECK(L.batch >= 1 && L.batch <= 65535, nm, ": batch ", L.batch,
+              " outside 1..65535");
+  TORCH_CHECK(a.size(0) == L.batch && b.size(0) == L.batch, nm,
+              ": a, b and c must have one batch size");
+  TORCH_CHECK(b.size(1) == L.K, nm, ": a is (B,K,M) and b must be (B,K,N)");
+  TORCH_CHECK(c.size(1) == L.N && c.size(2) == L.M, nm,
+              ": c must be (B,N,M) for column-major MxN");
+  TORCH_CHECK(L.M >= 1 && L.N >= 1 && L.K >= 1, nm, ": empty matrix");
+  for (const at::Tensor* t : {&a, &b, &c})
+    TORCH_CHECK(t->stride(2) == 1 && t->stride(1) == t->size(2), nm,
+                ": the two inner dimensions must be contiguous");
+  if (L.batch == 1) L.sA = L.sB = 0, L.sC = L.M * L.N;  // strides unused
+  TORCH_CHECK(L.sA >= 0 && L.sB >= 0 && L.sA % 4 == 0 && L.sB % 4 == 0 &&
+                  L.sC % 4 == 0,
+              nm, ": batch strides must be multiples of 4 floats (", L.sA,
+              ", ", L.sB, ", ", L.sC, ")");
+  TORCH_CHECK(L.sC >= L.M * L.N, nm,
+              ": c entries must not overlap (batch stride ", L.sC, " < ",
+              L.M * L.N, ")");
+  for (const at::Tensor* t : {&a, &b, &c})
+    TORCH_CHECK(((uintptr_t)t->data_ptr() & 15) == 0, nm,
+                ": tensors must be 16-byte aligned");
+  return L;
+}
+
+// Floats of segment-checksum scratch a fused sgemm_batched call on these
+// tensors asks the allocator for: one matrix's worth when a is shared
+// (batch stride 0), `batch` of them otherwise.
+int64_t batched_workspace_floats(int64_t tier, const at::Tensor& a,
+                                 const at::Tensor& b, const at::Tensor& c) {
+  const BatchedLayout L = check_batched_inputs(a, b, c);
+  const int nA = L.sA == 0 ? 1 : (int)L.batch;
+  return (int64_t)ftsgemm::sgemm_abft_workspace_floats_batched(
+      (int)tier, (int)L.M, (int)L.N, (int)L.K, nA);
+}
+
+// Strided-batched twin of sgemm: one launch for the whole batch.  counters
+// (B, 5) / events (B, capacity, 8): one fault log per entry.
+void sgemm_batched(int64_t tier, bool abft, bool inject, at::Tensor a,
+                   at::Tensor b, at::Tensor c, double alpha, double beta,
+                   double tau, double inj_mag, int64_t verify_windows,
+                   c10::optional<at::Tensor> counters,
+                   c10::optional<at::Tensor> events) {
+  const char* nm = "ft_sgemm_batched";
+  const BatchedLayout L = check_batched_inputs(a, b, c);
+  TORCH_CHECK(counters.has_value() == events.has_value(), nm,
+              ": fault-log counters and events go together");
+  ftsgemm::FaultLog flog;
+  if (counters.has_value()) {
+    const at::Tensor& cn = *counters;
+    const at::Tensor& ev = *events;
+    TORCH_CHECK(abft, nm, ": a fault log needs a fused-ABFT kernel");
+    TORCH_CHECK(cn.scalar_type() == at::kInt && ev.scalar_type() == at::kInt,
+                nm, ": fault-log tensors must be int32");
+    TORCH_CHECK(cn.is_contiguous() && ev.is_contiguous(), nm,
+                ": fault-log tensors must be contiguous");
+    TORCH_CHECK(cn.device() == a.device() && ev.device() == a.device(), nm,
+                ": fault-log tensors must be on the operands' device");
+    TORCH_CHECK(cn.dim() == 2 && cn.size(0) == L.batch &&
+                    cn.size(1) == ftsgemm::FLOG_N_COUNTERS,
+                nm, ": fault-log counters must be (batch, ",
+                (int)ftsgemm::FLOG_N_COUNTERS, ") int32");
+    TORCH_CHECK(ev.dim() == 3 && ev.size(0) == L.batch &&
+                    ev.size(2) == ftsgemm::FLOG_EVENT_DWORDS &&
+                    ev.size(1) >= 1 && ev.size(1) <= (1 << 24),
+                nm, ": fault-log events must be (batch, capacity, ",
+                (int)ftsgemm::FLOG_EVENT_DWORDS, ") int32");
+    flog.counters = cn.mutable_data_ptr<int>();
+    flog.events = ev.mutable_data_ptr<int>();
+    flog.capacity = (int)ev.size(1);
+  }
+  TORCH_CHECK(ftsgemm::sgemm_tier_supported((int)tier, L.M, L.N, L.K), nm,
+              ": tier ", tier, " requires M,N,K multiples of its tile (M=",
+              L.M, " N=", L.N, " K=", L.K, ")");
+  auto stream = at::cuda::getCurrentCUDAStream();
+  ftsgemm::GemmArgs g{abft, inject, (int)L.M, (int)L.N, (int)L.K,
+                      a.const_data_ptr<float>(), b.const_data_ptr<float>(),
+                      c.mutable_data_ptr<float>(), (float)alpha, (float)beta,
+                      (float)tau, (float)inj_mag, (int)verify_windows};
+  g.stream = stream.stream();
+  g.log = flog.counters ? &flog : nullptr;
+  g.batch = (int)L.batch;
+  g.strideA = L.sA;
+  g.strideB = L.sB;
+  g.strideC = L.sC;
+  at::Tensor ws;
+  if (abft) {
+    ws = at::empty({batched_workspace_floats(tier, a, b, c)}, a.options());
+    g.ws = ws.mutable_data_ptr<float>();
+  }
+  hipError_t err = ftsgemm::sgemm_tier_launch((int)tier, g);
+  TORCH_CHECK(err == hipSuccess, nm,
+              " launch failed: ", hipGetErrorString(err));
+}
+
 void rocblas_sgemm_nt(at::Tensor a, at::Tensor b, at::Tensor c, double alpha,
                       double beta) {
   int64_t M, N, K;
@@ -228,6 +346,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("b"), py::arg("c"), py::arg("alpha"), py::arg("beta"),
         py::arg("tau"), py::arg("inj_mag"), py::arg("verify_windows"),
         py::arg("counters") = py::none(), py::arg("events") = py::none());
+  m.def("sgemm_batched", &sgemm_batched,
+        "strided-batched tiered MFMA SGEMM, one launch per batch",
+        py::arg("tier"), py::arg("abft"), py::arg("inject"), py::arg("a"),
+        py::arg("b"), py::arg("c"), py::arg("alpha"), py::arg("beta"),
+        py::arg("tau"), py::arg("inj_mag"), py::arg("verify_windows"),
+        py::arg("counters") = py::none(), py::arg("events") = py::none());
+  m.def("batched_workspace_floats", &batched_workspace_floats,
+        "ABFT scratch floats a fused sgemm_batched call allocates");
   m.def("rocblas_sgemm", &rocblas_sgemm_nt, "rocBLAS oracle SGEMM");
   m.def("baseline_ft", &baseline_ft, "non-fused rocBLAS ABFT baseline");
   m.def("tier_supported", &tier_supported, "tile divisibility check");

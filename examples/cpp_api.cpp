@@ -36,5 +36,25 @@ int main() {
   }
   hipDeviceSynchronize();
   printf("fused-ABFT GEMM done\n");
+
+  // the same buffers as a strided batch of four 1024^3 products, one launch:
+  // A shared by every entry (strideA = 0, encoded once, so one matrix's
+  // workspace is enough), B and C four consecutive 1024 x 1024 blocks
+  const int nb = 1024;
+  ftsgemm::GemmArgs gb{/*abft=*/true, /*inject=*/false, nb, nb, nb, dA, dB, dC,
+                       1.f, 0.f, 9500.f, 10000.f, 20, ws};
+  gb.batch = 4;
+  gb.strideA = 0;
+  gb.strideB = gb.strideC = (long long)nb * nb;
+  if (ftsgemm::sgemm_abft_workspace_floats_batched(FT_TIER_ID_huge, nb, nb,
+                                                   nb, /*nA=*/1) > wsf)
+    return 1;
+  err = ftsgemm::sgemm_tier_launch(FT_TIER_ID_huge, gb);
+  if (err != hipSuccess) {
+    fprintf(stderr, "batched launch failed: %s\n", hipGetErrorString(err));
+    return 1;
+  }
+  hipDeviceSynchronize();
+  printf("strided-batched fused-ABFT GEMM done\n");
   return 0;
 }

@@ -68,5 +68,25 @@ block_row_sgemm(a, b, c, panel_k=1024,
                 gemm_fn=lambda ap, bp, cl, al, be:
                     ops.ft_sgemm("huge", ap, bp, cl, al, be, inject=True))
 
+# 7. strided batch: 16 independent 1024^3 products in ONE launch (plus one
+#    checksum-encode launch).  a:(B,K,M) b:(B,K,N) c:(B,N,M); a 2-D or
+#    expand()ed operand is shared by all entries, padded batch strides are
+#    fine (multiples of 4 floats).  One fault log per entry.
+ab = torch.rand((16, 1024, 1024), device="cuda")
+bb = torch.rand((16, 1024, 1024), device="cuda")
+cb = torch.zeros((16, 1024, 1024), device="cuda")
+ops.sgemm_batched("large", ab, bb, cb)
+breport = ops.BatchedFaultReport(batch=16)
+ops.ft_sgemm_batched("large", ab[0], bb, cb, inject=True, report=breport)
+print("per-entry corrected faults:", [r.corrected for r in breport.read()])
+breport.raise_if_uncorrected()  # names the entries it could not repair
+
+#    the distributed path's per-rank-chunk loop is such a batch:
+block_row_sgemm(a, b, c, panel_k=1024,
+                gemm_fn=lambda ap, bp, cl, al, be:
+                    ops.ft_sgemm("huge", ap, bp, cl, al, be, inject=True),
+                batched_gemm_fn=lambda ap, bs, cs, al, be:
+                    ops.ft_sgemm_batched("huge", ap, bs, cs, al, be))
+
 torch.cuda.synchronize()
 print("examples OK")

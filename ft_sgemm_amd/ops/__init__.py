@@ -13,9 +13,9 @@ import torch
 
 from ..kernel_table import (ERR_BOUND, ERROR_INJECT, KERNEL_TABLE, TIERS)
 from . import golden  # noqa: F401
-from .fault_report import (FaultCounts, FaultEvent, FaultReport,  # noqa: F401
-                           InjectionModel, predict_injected_events,
-                           predict_injection_model)
+from .fault_report import (BatchedFaultReport, FaultCounts,  # noqa: F401
+                           FaultEvent, FaultReport, InjectionModel,
+                           predict_injected_events, predict_injection_model)
 
 _C = None
 _load_err = None
@@ -73,6 +73,110 @@ def ft_sgemm(tier: str, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
         _require_ext().sgemm(tier_index(tier), True, inject, a, b, c,
                              alpha, beta, tau, inj_mag, verify_windows,
                              report.counters, report.events)
+    return c
+
+
+MAX_BATCH = 65535  # the batch index rides in gridDim.z
+
+
+def batched_layout(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor):
+    """Validate the operands of a strided-batched call and return
+    (batch, m, n, k, sA, sB, sC), the batch strides in floats.  Runs on any
+    device; the C++ binding repeats the same checks.
+
+    a is (B, K, M) or (K, M), b is (B, K, N) or (K, N), c is (B, N, M).  A
+    2-D operand is shared by every entry (stride 0), exactly like an
+    expand()ed one.  The two inner dimensions must be contiguous; the batch
+    stride is whatever the tensor has, so padded and expand()ed views pass
+    without a copy.  Every stride must be a multiple of 4 floats and every
+    tensor 16-byte aligned (16-B staging loads, f32x4 epilogue); c's entries
+    must not overlap (stride >= M*N).  Raises ValueError."""
+    def err(msg):
+        raise ValueError(f"sgemm_batched: {msg}")
+
+    if c.dim() != 3:
+        err(f"c must be (B, N, M), got {tuple(c.shape)}")
+    batch, n, m = c.shape
+    if not 1 <= batch <= MAX_BATCH:
+        err(f"batch {batch} outside 1..{MAX_BATCH}")
+    strides = []
+    for name, x in (("a", a), ("b", b)):
+        if x.dim() not in (2, 3):
+            err(f"{name} must be 2-D or 3-D, got {tuple(x.shape)}")
+        if x.dim() == 3 and x.shape[0] != batch:
+            err(f"batch mismatch: {name} has {x.shape[0]} entries, c {batch}")
+    k = a.shape[-2]
+    if a.shape[-1] != m or tuple(b.shape[-2:]) != (k, n):
+        err(f"a (.., K, M) = {tuple(a.shape)}, b (.., K, N) = "
+            f"{tuple(b.shape)} and c (B, N, M) = {tuple(c.shape)} disagree")
+    if min(m, n, k) < 1:
+        err("empty matrix")
+    for name, x in (("a", a), ("b", b), ("c", c)):
+        if x.dtype != torch.float32:
+            err(f"{name} must be float32")
+        if x.stride(-1) != 1 or x.stride(-2) != x.shape[-1]:
+            err(f"the two inner dimensions of {name} must be contiguous "
+                f"(strides {tuple(x.stride())})")
+        if x.data_ptr() % 16:
+            err(f"{name} must be 16-byte aligned")
+        strides.append(x.stride(0) if x.dim() == 3 and batch > 1 else 0)
+    sa, sb, sc = strides
+    if batch == 1:
+        sc = m * n  # a single entry: the strides are not used
+    if sa < 0 or sb < 0 or sa % 4 or sb % 4 or sc % 4:
+        err(f"batch strides ({sa}, {sb}, {sc}) must be multiples of 4 floats")
+    if sc < m * n:
+        err(f"c entries overlap or are broadcast (batch stride {sc} < "
+            f"M*N = {m * n})")
+    return batch, m, n, k, sa, sb, sc
+
+
+def _batched_operands(a, b, c):
+    """(a, b) as the 3-D views the binding takes, after batched_layout."""
+    batch = batched_layout(a, b, c)[0]
+    return tuple(x if x.dim() == 3 else x.unsqueeze(0).expand(batch, -1, -1)
+                 for x in (a, b))
+
+
+def sgemm_batched(tier: str, a: torch.Tensor, b: torch.Tensor,
+                  c: torch.Tensor, alpha: float = 1.0,
+                  beta: float = 0.0) -> torch.Tensor:
+    """Strided-batched plain SGEMM, one launch: for every entry i,
+    c[i] = alpha * A_i B_i^T + beta * c[i] in sgemm's storage convention.
+    a:(B,K,M) b:(B,K,N) c:(B,N,M), layout rules in batched_layout; a 2-D a
+    or b is shared by all entries.  Each entry's result has the bits of
+    sgemm on that entry with the classic (non-stream-K) decomposition;
+    FT_SGEMM_STREAMK has no effect on a batch of more than one."""
+    a3, b3 = _batched_operands(a, b, c)
+    _require_ext().sgemm_batched(tier_index(tier), False, False, a3, b3, c,
+                                 alpha, beta, 0.0, 0.0, 20)
+    return c
+
+
+def ft_sgemm_batched(tier: str, a: torch.Tensor, b: torch.Tensor,
+                     c: torch.Tensor, alpha: float = 1.0, beta: float = 0.0,
+                     inject: bool = True, tau: float = ERR_BOUND,
+                     inj_mag: float = ERROR_INJECT, verify_windows: int = 20,
+                     report: BatchedFaultReport | None = None
+                     ) -> torch.Tensor:
+    """Strided-batched fused-ABFT SGEMM, one checksum-encode launch and one
+    GEMM launch for the whole batch; arguments as ft_sgemm, layout as
+    sgemm_batched.  A shared a (2-D or expand()ed) is encoded once.  The
+    injector rotates per entry, as in ft_sgemm.  report: a
+    BatchedFaultReport of the same batch size; entry i logs into slot i."""
+    a3, b3 = _batched_operands(a, b, c)
+    if report is None:
+        _require_ext().sgemm_batched(tier_index(tier), True, inject, a3, b3,
+                                     c, alpha, beta, tau, inj_mag,
+                                     verify_windows)
+    else:
+        if report.batch != c.shape[0]:
+            raise ValueError(f"ft_sgemm_batched: report holds {report.batch} "
+                             f"entries, the batch {c.shape[0]}")
+        _require_ext().sgemm_batched(tier_index(tier), True, inject, a3, b3,
+                                     c, alpha, beta, tau, inj_mag,
+                                     verify_windows, report.counters,
+                                     report.events)
     return c
 
 
@@ -145,7 +249,7 @@ def detect_selftest(fm: int, fn: int, mm: int, idesc: torch.Tensor,
     return _require_ext().detect_selftest(fm, fn, mm, idesc, fdesc, amp)
 
 
-def choose_tier(m: int, n: int, k: int):
+def choose_tier(m: int, n: int, k: int, batch: int = 1):
     """Pick the fastest applicable tier for a problem shape, or None when no
     hand-tiled tier divides the shape (callers fall back to rocBLAS).
 
@@ -153,24 +257,44 @@ def choose_tier(m: int, n: int, k: int):
     (profiles/cli_sweep_r2.log, stream-K-enabled kernels): the huge
     256x128 macro-tile wins from ~384 tiles up (its stream-K twin covers
     the tail-waste sizes), the large 64x64 tier wins the 2048-3072 band
-    (>=1024 blocks), and below that the medium tier's dense grid wins."""
+    (>=1024 blocks), and below that the medium tier's dense grid wins.
+
+    batch: entries of a strided-batched launch (sgemm_batched /
+    ft_sgemm_batched).  batch == 1 gives exactly the single-launch answers
+    above.  For batch > 1 the same thresholds are applied to the grid the
+    launch really has, tiles x batch workgroups: in the four measured cells
+    of profiles/batched_bmm.txt (512^3 x64, 1024^3 x16, 2048^3 x4 -> huge;
+    block_row panel 1024x1024x512 x8 -> large) that picks the fastest tier.
+    BATCHED_THRESHOLDS_NOTE has the details and what is not measured."""
     from .. import kernel_table as kt
 
     def fits(tier):
         t = kt.TILING[tier]
         return m % t["bm"] == 0 and n % t["bn"] == 0 and k % t["bk"] == 0
 
-    if fits("huge") and (m // 256) * (n // 128) >= 384:
+    if fits("huge") and (m // 256) * (n // 128) * batch >= 384:
         return "huge"
     skinny = ("tall" if m >= 4 * n else "wide" if n >= 4 * m else None)
     if skinny and fits(skinny):
         return skinny
-    if fits("large") and (m // 64) * (n // 64) >= 1024:
+    if fits("large") and (m // 64) * (n // 64) * batch >= 1024:
         return "large"
     for tier in ("medium", "large", "small"):
         if fits(tier):
             return tier
     return None
+
+
+# How choose_tier's batch > 1 answers were arrived at.
+BATCHED_THRESHOLDS_NOTE = (
+    "measured (profiles/batched_bmm.txt, MI355X, one batched launch, plain "
+    "and fused no-inject): the single-launch tile-count thresholds applied "
+    "to tiles x batch pick the fastest measured tier in all four cells — "
+    "512^3 x64, 1024^3 x16 and 2048^3 x4 (each 512 huge tiles x batch: huge "
+    "is 16-22% ahead of the next tier) and the block_row panel 1024x1024x512 "
+    "x8 (256 huge tiles x batch, below 384: large, 1-2% ahead of huge).  "
+    "Grids between 256 and 512 huge tiles and skinny batched shapes are "
+    "not measured")
 
 
 def sgemm_auto(a, b, c, alpha: float = 1.0, beta: float = 0.0):
@@ -250,3 +374,14 @@ def torch_reference(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
     """Plain fp32 PyTorch reference of the same op: c' = alpha*(b^T a) + beta*c
     (in our storage convention this IS C = alpha*A B^T + beta*C)."""
     return alpha * (b.transpose(0, 1) @ a) + beta * c
+
+
+def torch_reference_batched(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
+                            alpha: float = 1.0,
+                            beta: float = 0.0) -> torch.Tensor:
+    """torch.bmm form of torch_reference for a:(B,K,M) b:(B,K,N) c:(B,N,M);
+    a 2-D a or b is shared by all entries."""
+    batch = c.shape[0]
+    a3, b3 = (x if x.dim() == 3 else x.unsqueeze(0).expand(batch, -1, -1)
+              for x in (a, b))
+    return alpha * torch.bmm(b3.transpose(1, 2), a3) + beta * c

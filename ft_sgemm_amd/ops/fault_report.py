@@ -117,6 +117,51 @@ class FaultReport:
                 f"result holds corruption that was detected but not repaired")
 
 
+class BatchedFaultReport:
+    """Caller-owned fault logs for ops.ft_sgemm_batched(..., report=...):
+    one FaultReport-shaped log per batch entry, in the two tensors the
+    batched kernels write — counters (batch, 5) and events (batch, capacity,
+    8), int32.  Entry i of the batch reports into slot i and nowhere else.
+    Accumulates across launches until reset(), like FaultReport."""
+
+    def __init__(self, batch: int, capacity: int = 1024, device="cuda"):
+        if batch < 1:
+            raise ValueError("BatchedFaultReport: batch must be >= 1")
+        if capacity < 1:
+            raise ValueError("BatchedFaultReport: capacity must be >= 1")
+        self.batch = int(batch)
+        self.capacity = int(capacity)
+        self.counters = torch.zeros((self.batch, N_COUNTERS),
+                                    dtype=torch.int32, device=device)
+        self.events = torch.zeros((self.batch, self.capacity, EVENT_DWORDS),
+                                  dtype=torch.int32, device=device)
+
+    def reset(self) -> None:
+        """Zero every log on the device, in stream order (no host sync)."""
+        self.counters.zero_()
+        self.events.zero_()
+
+    def read(self) -> List[FaultCounts]:
+        """Synchronise once and return one FaultCounts per batch entry."""
+        if self.counters.is_cuda:
+            torch.cuda.synchronize(self.counters.device)
+        counters, events = self.counters.to("cpu"), self.events.to("cpu")
+        return [decode(counters[i], events[i]) for i in range(self.batch)]
+
+    def raise_if_uncorrected(self) -> None:
+        """Refuse a batch in which some entry could not be repaired."""
+        bad = [(i, r) for i, r in enumerate(self.read())
+               if r.uncorrected or r.unlocated]
+        if bad:
+            detail = ", ".join(
+                f"entry {i}: {r.uncorrected} uncorrected, {r.unlocated} "
+                f"unlocated of {r.tripped} tripped" for i, r in bad)
+            raise RuntimeError(
+                f"fused ABFT (batched): batch entries "
+                f"{[i for i, _ in bad]} hold corruption that was detected "
+                f"but not repaired ({detail})")
+
+
 def predict_injected_events(tier: str, m: int, n: int, k: int,
                             verify_windows: int = 20) -> List[FaultEvent]:
     """The exact events the classic fused kernel's injector must produce for

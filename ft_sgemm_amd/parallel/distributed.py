@@ -61,7 +61,9 @@ def block_row_sgemm(a_local: torch.Tensor, b_local: torch.Tensor,
                     c_local: torch.Tensor, *, panel_k: int,
                     gemm_fn: Callable[..., None], alpha: float = 1.0,
                     beta: float = 0.0,
-                    group: Optional[dist.ProcessGroup] = None) -> torch.Tensor:
+                    group: Optional[dist.ProcessGroup] = None,
+                    batched_gemm_fn: Optional[Callable[..., None]] = None
+                    ) -> torch.Tensor:
     """Block-row distributed C = alpha * A @ B^T + beta * C.
 
     Shard layout (column-major semantics, tensors in the package's
@@ -74,6 +76,14 @@ def block_row_sgemm(a_local: torch.Tensor, b_local: torch.Tensor,
     gather of panel p+1 is issued asynchronously before the local GEMM of
     panel p, so RCCL traffic over xGMI overlaps MFMA compute.  `gemm_fn`
     accumulates one panel: gemm_fn(a_panel, b_panel, c_local, alpha, beta).
+
+    batched_gemm_fn (optional): on the gathered path the `world` rank-chunks
+    of a panel are a strided batch — a_panel shared, B the stacked
+    (world, panel_k, n_loc) gather buffer, C the equally spaced row blocks
+    c_local.view(world, n_loc, M_loc) — so when given, one
+    batched_gemm_fn(a_panel, buf, c_view, alpha, beta) call per panel
+    replaces the loop of `world` gemm_fn calls (ops.ft_sgemm_batched /
+    ops.sgemm_batched with a tier bound; torch_batched_gemm_fn on the CPU).
     """
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     k = a_local.shape[0]
@@ -114,10 +124,15 @@ def block_row_sgemm(a_local: torch.Tensor, b_local: torch.Tensor,
         work.wait()
         a_panel = a_local[p * panel_k:(p + 1) * panel_k].contiguous()
         b0 = beta if p == 0 else 1.0
-        for rr in range(world):
-            # chunk rr covers C rows (= output columns) [rr*n_loc, +n_loc)
-            gemm_fn(a_panel, buf[rr], c_local[rr * n_loc:(rr + 1) * n_loc],
-                    alpha, b0)
+        if batched_gemm_fn is not None:
+            batched_gemm_fn(a_panel, buf,
+                            c_local.view(world, n_loc, c_local.shape[1]),
+                            alpha, b0)
+        else:
+            for rr in range(world):
+                # chunk rr covers C rows (= output columns) [rr*n_loc, +n_loc)
+                gemm_fn(a_panel, buf[rr],
+                        c_local[rr * n_loc:(rr + 1) * n_loc], alpha, b0)
         if nxt is not None:
             buf, work = nxt
     return c_local
@@ -133,3 +148,17 @@ def torch_gemm_fn(a_panel, b_panel, c_local, alpha, beta):
         c_local.copy_(prod)
     else:
         c_local.mul_(beta).add_(prod)
+
+
+def torch_batched_gemm_fn(a_panel, b_stack, c_stack, alpha, beta):
+    """torch.bmm reference of block_row_sgemm's batched_gemm_fn: a_panel
+    (panel_k, M_loc) shared, b_stack (world, panel_k, n_loc), c_stack
+    (world, n_loc, M_loc) a view of c_local, updated in place.  beta == 0
+    overwrites without reading, like torch_gemm_fn."""
+    prod = alpha * torch.bmm(
+        b_stack.transpose(1, 2),
+        a_panel.unsqueeze(0).expand(b_stack.shape[0], -1, -1))
+    if beta == 0:
+        c_stack.copy_(prod)
+    else:
+        c_stack.mul_(beta).add_(prod)

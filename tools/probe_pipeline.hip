@@ -280,13 +280,15 @@ static void run_lib(const char* name, int n, const float* dA, const float* dB,
           (ftsgemm::sgemm_mfma<BM_, BN_, BK_, WM_, WN_, MM_, ABFT_, INJ_,
                                OCC_>),
           grid, block, 0, 0, n, n, n, dA, dB, dC, 1.f, beta_, stride, stride,
-          9500.f, 10000.f, ws, sstr, ftsgemm::FaultLog{});
+          9500.f, 10000.f, ws, sstr, ftsgemm::FaultLog{},
+          ftsgemm::BatchStrides{});
     } else {
       hipLaunchKernelGGL(
           (ftsgemm::sgemm_mfma<BM_, BN_, BK_, WM_, WN_, MM_, false, false,
                                OCC_>),
           grid, block, 0, 0, n, n, n, dA, dB, dC, 1.f, beta_, stride, stride,
-          1e30f, 0.f, nullptr, 0, ftsgemm::FaultLog{});
+          1e30f, 0.f, nullptr, 0, ftsgemm::FaultLog{},
+          ftsgemm::BatchStrides{});
     }
   };
   hipMemsetD32Async((hipDeviceptr_t)dC, 0, (size_t)n * n, 0);
