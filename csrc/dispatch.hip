@@ -14,7 +14,9 @@ namespace ftsgemm {
 #define FT_DECL(name, BM, BN, BK, WM, WN, MM)              \
   hipError_t launch_tier_##name(const GemmArgs& g);         \
   hipError_t launch_tier_batched_##name(const GemmArgs& g); \
-  size_t abft_ws_floats_##name(int M, int N, int K);
+  hipError_t launch_tier_ragged_##name(const GemmArgs& g);  \
+  size_t abft_ws_floats_##name(int M, int N, int K);        \
+  size_t abft_ws_floats_ragged_##name(int M, int N, int K);
 FT_TIER_LIST(FT_DECL)
 #undef FT_DECL
 
@@ -25,13 +27,16 @@ namespace {
 struct TierRow {
   hipError_t (*launch)(const GemmArgs&);
   hipError_t (*launch_batched)(const GemmArgs&);  // batch > 1
+  hipError_t (*launch_ragged)(const GemmArgs&);   // g.ragged
   size_t (*ws_floats)(int, int, int);
+  size_t (*ws_floats_ragged)(int, int, int);
   int bm, bn, bk;
 };
 const TierRow kTiers[FT_N_TIERS] = {
-#define FT_ROW(name, BM, BN, BK, WM, WN, MM)                             \
-  {launch_tier_##name, launch_tier_batched_##name, abft_ws_floats_##name, \
-   BM, BN, BK},
+#define FT_ROW(name, BM, BN, BK, WM, WN, MM)                   \
+  {launch_tier_##name,    launch_tier_batched_##name,           \
+   launch_tier_ragged_##name, abft_ws_floats_##name,            \
+   abft_ws_floats_ragged_##name, BM, BN, BK},
     FT_TIER_LIST(FT_ROW)
 #undef FT_ROW
 };
@@ -45,7 +50,20 @@ const TierRow* tier_row(int tier) {
 hipError_t sgemm_tier_launch(int tier, const GemmArgs& g) {
   const TierRow* t = tier_row(tier);
   if (!t || g.batch < 1) return hipErrorInvalidValue;
+  if (g.ragged) {
+    // one product only; a leading dimension may pad its rows, never cut them
+    if (g.batch > 1) return hipErrorInvalidValue;
+    if ((g.lda && g.lda < g.M) || (g.ldb && g.ldb < g.N) ||
+        (g.ldc && g.ldc < g.M))
+      return hipErrorInvalidValue;
+    return t->launch_ragged(g);
+  }
   return g.batch > 1 ? t->launch_batched(g) : t->launch(g);
+}
+
+size_t sgemm_abft_workspace_floats_ragged(int tier, int M, int N, int K) {
+  const TierRow* t = tier_row(tier);
+  return t && M > 0 && N > 0 && K > 0 ? t->ws_floats_ragged(M, N, K) : 0;
 }
 
 // Workspace floats needed by the fused-ABFT path of a tier (the segment-sum

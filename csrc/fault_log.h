@@ -18,7 +18,11 @@ enum FaultCounter {
   FLOG_N_COUNTERS = 5
 };
 
-// Event record, FLOG_EVENT_DWORDS int32 each.
+// Event record, FLOG_EVENT_DWORDS int32 each.  Coordinates are those of the
+// tile grid.  In a ragged launch (ft_ragged.hpp) an edge tile reaches past
+// the matrix, and a fault absorbed in that zero padding is corrected and
+// logged like any other, with its true padded coordinates: i >= M or j >= N
+// is possible there, and k_end, a whole number of panels, may exceed K.
 enum FaultEventField {
   FLOG_EV_I = 0,         // global row of the faulty element, -1 if unknown
   FLOG_EV_J = 1,         // global column of the faulty element

@@ -32,6 +32,14 @@ namespace ftsgemm {
 // A batched launch always takes the classic tile-per-workgroup path
 // (FT_SGEMM_STREAMK has no effect on it); batch == 1 is today's launch and
 // ignores the strides.
+//
+// ragged lifts the shape and layout rules of a single product: any
+// M, N, K >= 1, A with leading dimension lda >= M, B with ldb >= N, C with
+// ldc >= M (0 = packed), base pointers with only fp32 alignment.  The ragged
+// twin of the classic kernel runs (ft_ragged.hpp) on ceil tile counts; ws then
+// holds sgemm_abft_workspace_floats_ragged(tier, M, N, K) floats.  ragged
+// with batch > 1 is rejected.  A fault injected into an edge tile's padding
+// is logged with its padded coordinates (fault_log.h).
 struct GemmArgs {
   bool abft, inject;
   int M, N, K;
@@ -44,6 +52,8 @@ struct GemmArgs {
   const FaultLog* log = nullptr;
   int batch = 1;
   long long strideA = 0, strideB = 0, strideC = 0;
+  bool ragged = false;
+  int lda = 0, ldb = 0, ldc = 0;  // ragged only; 0 = packed
 };
 
 // Launch tier `tier` (id per generated/tile_params.h).
@@ -56,6 +66,9 @@ size_t sgemm_abft_workspace_floats(int tier, int M, int N, int K);
 // nA consecutive copies of the per-matrix workspace (GemmArgs note).
 size_t sgemm_abft_workspace_floats_batched(int tier, int M, int N, int K,
                                            int nA);
+
+// Workspace of a fused ragged launch: 2 * ceil(M/WM) * round_up(K, 64).
+size_t sgemm_abft_workspace_floats_ragged(int tier, int M, int N, int K);
 
 // Device self-test of the fused kernels' shared detect / locate / correct
 // (locate_selftest.hip): one single-wave block per case plants up to two

@@ -204,6 +204,111 @@ void sgemm_batched(int64_t tier, bool abft, bool inject, at::Tensor a,
               " launch failed: ", hipGetErrorString(err));
 }
 
+// Layout of a ragged call (mirrors ops.ragged_layout, the Python helper that
+// raises ValueError before a call gets here): a (K,M), b (K,N), c (N,M), any
+// sizes >= 1, unit inner stride, row stride >= row width.  The row stride is
+// the column-major leading dimension; a one-row tensor's is its width.
+struct RaggedLayout {
+  int64_t M, N, K, lda, ldb, ldc;
+};
+
+RaggedLayout check_ragged_inputs(const at::Tensor& a, const at::Tensor& b,
+                                 const at::Tensor& c) {
+  const char* nm = "ft_sgemm_ragged";
+  TORCH_CHECK(a.is_cuda() && b.is_cuda() && c.is_cuda(), nm,
+              ": tensors must be on a GPU device");
+  TORCH_CHECK(a.device() == b.device() && a.device() == c.device(), nm,
+              ": tensors must be on one device");
+  TORCH_CHECK(a.scalar_type() == at::kFloat &&
+                  b.scalar_type() == at::kFloat &&
+                  c.scalar_type() == at::kFloat,
+              nm, ": fp32 only (SGEMM)");
+  TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && c.dim() == 2, nm,
+              ": 2-D tensors a (K,M), b (K,N), c (N,M) expected");
+  RaggedLayout L{a.size(1), b.size(1), a.size(0), 0, 0, 0};
+  TORCH_CHECK(L.M >= 1 && L.N >= 1 && L.K >= 1, nm, ": empty matrix");
+  TORCH_CHECK(b.size(0) == L.K, nm, ": a is (K,M) and b must be (K,N)");
+  TORCH_CHECK(c.size(0) == L.N && c.size(1) == L.M, nm,
+              ": c must be (N,M) for column-major MxN");
+  const auto ld = [&](const at::Tensor& t, const char* which) {
+    TORCH_CHECK(t.stride(1) == 1 || t.size(1) == 1, nm, ": ", which,
+                " must have a unit inner stride");
+    if (t.size(0) == 1) return t.size(1);
+    TORCH_CHECK(t.stride(0) >= t.size(1), nm, ": rows of ", which,
+                " overlap (row stride ", t.stride(0), " < ", t.size(1), ")");
+    TORCH_CHECK(t.stride(0) <= INT32_MAX, nm, ": row stride of ", which,
+                " too large");
+    return t.stride(0);
+  };
+  L.lda = ld(a, "a");
+  L.ldb = ld(b, "b");
+  L.ldc = ld(c, "c");
+  return L;
+}
+
+// Ragged twin of sgemm: any M, N, K and row-strided operands.
+void sgemm_ragged(int64_t tier, bool abft, bool inject, at::Tensor a,
+                  at::Tensor b, at::Tensor c, double alpha, double beta,
+                  double tau, double inj_mag, int64_t verify_windows,
+                  c10::optional<at::Tensor> counters,
+                  c10::optional<at::Tensor> events) {
+  const char* nm = "ft_sgemm_ragged";
+  const RaggedLayout L = check_ragged_inputs(a, b, c);
+  TORCH_CHECK(counters.has_value() == events.has_value(), nm,
+              ": fault-log counters and events go together");
+  ftsgemm::FaultLog flog;
+  if (counters.has_value()) {
+    const at::Tensor& cn = *counters;
+    const at::Tensor& ev = *events;
+    TORCH_CHECK(abft, nm, ": a fault log needs a fused-ABFT kernel");
+    TORCH_CHECK(cn.scalar_type() == at::kInt && ev.scalar_type() == at::kInt,
+                nm, ": fault-log tensors must be int32");
+    TORCH_CHECK(cn.is_contiguous() && ev.is_contiguous(), nm,
+                ": fault-log tensors must be contiguous");
+    TORCH_CHECK(cn.device() == a.device() && ev.device() == a.device(), nm,
+                ": fault-log tensors must be on the operands' device");
+    TORCH_CHECK(cn.dim() == 1 && cn.size(0) >= ftsgemm::FLOG_N_COUNTERS, nm,
+                ": fault-log counters must hold ",
+                (int)ftsgemm::FLOG_N_COUNTERS, " int32");
+    TORCH_CHECK(ev.dim() == 2 && ev.size(1) == ftsgemm::FLOG_EVENT_DWORDS &&
+                    ev.size(0) <= (1 << 24),
+                nm, ": fault-log events must be (capacity, ",
+                (int)ftsgemm::FLOG_EVENT_DWORDS, ") int32");
+    flog.counters = cn.mutable_data_ptr<int>();
+    flog.events = ev.mutable_data_ptr<int>();
+    flog.capacity = (int)ev.size(0);
+  }
+  TORCH_CHECK(L.M <= INT32_MAX && L.N <= INT32_MAX && L.K <= INT32_MAX - 64,
+              nm, ": a size beyond int32");
+  auto stream = at::cuda::getCurrentCUDAStream();
+  ftsgemm::GemmArgs g{abft, inject, (int)L.M, (int)L.N, (int)L.K,
+                      a.const_data_ptr<float>(), b.const_data_ptr<float>(),
+                      c.mutable_data_ptr<float>(), (float)alpha, (float)beta,
+                      (float)tau, (float)inj_mag, (int)verify_windows};
+  g.stream = stream.stream();
+  g.log = flog.counters ? &flog : nullptr;
+  g.ragged = true;
+  g.lda = (int)L.lda;
+  g.ldb = (int)L.ldb;
+  g.ldc = (int)L.ldc;
+  at::Tensor ws;
+  if (abft) {
+    size_t n = ftsgemm::sgemm_abft_workspace_floats_ragged(
+        (int)tier, (int)L.M, (int)L.N, (int)L.K);
+    ws = at::empty({(int64_t)n}, a.options());
+    g.ws = ws.mutable_data_ptr<float>();
+  }
+  hipError_t err = ftsgemm::sgemm_tier_launch((int)tier, g);
+  TORCH_CHECK(err == hipSuccess, nm,
+              " launch failed: ", hipGetErrorString(err));
+}
+
+int64_t ragged_workspace_floats(int64_t tier, int64_t M, int64_t N,
+                                int64_t K) {
+  return (int64_t)ftsgemm::sgemm_abft_workspace_floats_ragged(
+      (int)tier, (int)M, (int)N, (int)K);
+}
+
 void rocblas_sgemm_nt(at::Tensor a, at::Tensor b, at::Tensor c, double alpha,
                       double beta) {
   int64_t M, N, K;
@@ -354,6 +459,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("counters") = py::none(), py::arg("events") = py::none());
   m.def("batched_workspace_floats", &batched_workspace_floats,
         "ABFT scratch floats a fused sgemm_batched call allocates");
+  m.def("sgemm_ragged", &sgemm_ragged,
+        "tiered MFMA SGEMM for any M, N, K and row-strided operands",
+        py::arg("tier"), py::arg("abft"), py::arg("inject"), py::arg("a"),
+        py::arg("b"), py::arg("c"), py::arg("alpha"), py::arg("beta"),
+        py::arg("tau"), py::arg("inj_mag"), py::arg("verify_windows"),
+        py::arg("counters") = py::none(), py::arg("events") = py::none());
+  m.def("ragged_workspace_floats", &ragged_workspace_floats,
+        "ABFT scratch floats a fused sgemm_ragged call allocates");
   m.def("rocblas_sgemm", &rocblas_sgemm_nt, "rocBLAS oracle SGEMM");
   m.def("baseline_ft", &baseline_ft, "non-fused rocBLAS ABFT baseline");
   m.def("tier_supported", &tier_supported, "tile divisibility check");

@@ -56,5 +56,22 @@ int main() {
   }
   hipDeviceSynchronize();
   printf("strided-batched fused-ABFT GEMM done\n");
+
+  // a 1001 x 999 x 333 sub-block of the same buffers, starting one float in
+  // (4-byte alignment only) with the 2048 leading dimensions: a ragged launch
+  ftsgemm::GemmArgs gr{/*abft=*/true, /*inject=*/true, 1001, 999, 333, dA + 1,
+                       dB + 1, dC + 1, 1.f, 0.f, 9500.f, 10000.f, 20, ws};
+  gr.ragged = true;
+  gr.lda = gr.ldb = gr.ldc = n;
+  if (ftsgemm::sgemm_abft_workspace_floats_ragged(FT_TIER_ID_large, 1001, 999,
+                                                  333) > wsf)
+    return 1;
+  err = ftsgemm::sgemm_tier_launch(FT_TIER_ID_large, gr);
+  if (err != hipSuccess) {
+    fprintf(stderr, "ragged launch failed: %s\n", hipGetErrorString(err));
+    return 1;
+  }
+  hipDeviceSynchronize();
+  printf("ragged fused-ABFT GEMM done\n");
   return 0;
 }

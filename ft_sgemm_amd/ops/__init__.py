@@ -180,6 +180,84 @@ def ft_sgemm_batched(tier: str, a: torch.Tensor, b: torch.Tensor,
     return c
 
 
+def ragged_layout(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor):
+    """Validate the operands of a ragged call and return
+    (m, n, k, lda, ldb, ldc), the leading dimensions in floats.  Runs on any
+    device; the C++ binding repeats the same checks.
+
+    a is (K, M), b is (K, N), c is (N, M), fp32, any sizes >= 1.  The inner
+    stride must be 1 and the row stride at least the row width, so packed
+    tensors and row-strided views (x[k0:k1, m0:m1]) pass without a copy; the
+    row stride is the column-major leading dimension, and a one-row tensor's
+    is its width.  No alignment beyond fp32 is asked for.  c's rows must not
+    overlap.  Raises ValueError."""
+    def err(msg):
+        raise ValueError(f"sgemm_ragged: {msg}")
+
+    for name, x in (("a", a), ("b", b), ("c", c)):
+        if x.dim() != 2:
+            err(f"{name} must be 2-D, got {tuple(x.shape)}")
+        if x.dtype != torch.float32:
+            err(f"{name} must be float32")
+    k, m = a.shape
+    n = b.shape[1]
+    if b.shape[0] != k or tuple(c.shape) != (n, m):
+        err(f"a (K, M) = {tuple(a.shape)}, b (K, N) = {tuple(b.shape)} and "
+            f"c (N, M) = {tuple(c.shape)} disagree")
+    if min(m, n, k) < 1:
+        err("empty matrix")
+    lds = []
+    for name, x in (("a", a), ("b", b), ("c", c)):
+        if x.stride(1) != 1 and x.shape[1] != 1:
+            err(f"{name} must have a unit inner stride "
+                f"(strides {tuple(x.stride())})")
+        if x.shape[0] == 1:
+            lds.append(x.shape[1])
+            continue
+        if x.stride(0) < x.shape[1]:
+            err(f"rows of {name} overlap or are broadcast (row stride "
+                f"{x.stride(0)} < {x.shape[1]})")
+        lds.append(x.stride(0))
+    return (m, n, k, *lds)
+
+
+def sgemm_ragged(tier: str, a: torch.Tensor, b: torch.Tensor,
+                 c: torch.Tensor, alpha: float = 1.0,
+                 beta: float = 0.0) -> torch.Tensor:
+    """Plain SGEMM for any M, N, K >= 1 and row-strided operands (layout
+    rules in ragged_layout), on the ragged twin of `tier`'s classic kernel:
+    ceil tile counts, out-of-range operand elements staged as zeros, only the
+    M x N window of c written.  On a shape the tile divides the result has
+    the bits of sgemm with the classic (non-stream-K) decomposition.
+    In-place on c."""
+    ragged_layout(a, b, c)
+    _require_ext().sgemm_ragged(tier_index(tier), False, False, a, b, c,
+                                alpha, beta, 0.0, 0.0, 20)
+    return c
+
+
+def ft_sgemm_ragged(tier: str, a: torch.Tensor, b: torch.Tensor,
+                    c: torch.Tensor, alpha: float = 1.0, beta: float = 0.0,
+                    inject: bool = True, tau: float = ERR_BOUND,
+                    inj_mag: float = ERROR_INJECT, verify_windows: int = 20,
+                    report: FaultReport | None = None) -> torch.Tensor:
+    """Fused-ABFT SGEMM for any M, N, K >= 1 and row-strided operands:
+    ft_sgemm's in-kernel verify / locate / correct, injector self-test and
+    fault report without a tile fit; arguments as ft_sgemm, layout as
+    sgemm_ragged.  The injector keeps its per-block rule, so in an edge tile
+    a victim may lie in the padding: it is corrected like any other and
+    reported with its padded coordinates (FaultReport)."""
+    ragged_layout(a, b, c)
+    if report is None:
+        _require_ext().sgemm_ragged(tier_index(tier), True, inject, a, b, c,
+                                    alpha, beta, tau, inj_mag, verify_windows)
+    else:
+        _require_ext().sgemm_ragged(tier_index(tier), True, inject, a, b, c,
+                                    alpha, beta, tau, inj_mag, verify_windows,
+                                    report.counters, report.events)
+    return c
+
+
 def rocblas_sgemm(a, b, c, alpha: float = 1.0, beta: float = 0.0):
     """Kernel id 0: the vendor-BLAS oracle."""
     _require_ext().rocblas_sgemm(a, b, c, alpha, beta)
@@ -249,7 +327,8 @@ def detect_selftest(fm: int, fn: int, mm: int, idesc: torch.Tensor,
     return _require_ext().detect_selftest(fm, fn, mm, idesc, fdesc, amp)
 
 
-def choose_tier(m: int, n: int, k: int, batch: int = 1):
+def choose_tier(m: int, n: int, k: int, batch: int = 1,
+                ragged: bool = False):
     """Pick the fastest applicable tier for a problem shape, or None when no
     hand-tiled tier divides the shape (callers fall back to rocBLAS).
 
@@ -265,19 +344,38 @@ def choose_tier(m: int, n: int, k: int, batch: int = 1):
     launch really has, tiles x batch workgroups: in the four measured cells
     of profiles/batched_bmm.txt (512^3 x64, 1024^3 x16, 2048^3 x4 -> huge;
     block_row panel 1024x1024x512 x8 -> large) that picks the fastest tier.
-    BATCHED_THRESHOLDS_NOTE has the details and what is not measured."""
+    BATCHED_THRESHOLDS_NOTE has the details and what is not measured.
+
+    ragged: pick for sgemm_ragged / ft_sgemm_ragged.  Every tier then fits
+    every shape, so a tier is always returned: the same thresholds, applied
+    to the ceil tile counts of the grid the ragged launch has.  Where the
+    plain call returns a tier, this returns the same one.
+    RAGGED_THRESHOLDS_NOTE says what of this is measured."""
     from .. import kernel_table as kt
 
     def fits(tier):
         t = kt.TILING[tier]
-        return m % t["bm"] == 0 and n % t["bn"] == 0 and k % t["bk"] == 0
+        return ragged or (m % t["bm"] == 0 and n % t["bn"] == 0 and
+                          k % t["bk"] == 0)
 
-    if fits("huge") and (m // 256) * (n // 128) * batch >= 384:
+    def tiles(tier):
+        t = kt.TILING[tier]
+        return -(-m // t["bm"]) * -(-n // t["bn"])
+
+    if ragged:
+        if batch != 1 or min(m, n, k) < 1:
+            raise ValueError("choose_tier: a ragged launch is one product "
+                             "of sizes >= 1")
+        # a shape some tier divides keeps the tier its tiled launch gets
+        tiled = choose_tier(m, n, k)
+        if tiled is not None:
+            return tiled
+    if fits("huge") and tiles("huge") * batch >= 384:
         return "huge"
     skinny = ("tall" if m >= 4 * n else "wide" if n >= 4 * m else None)
     if skinny and fits(skinny):
         return skinny
-    if fits("large") and (m // 64) * (n // 64) * batch >= 1024:
+    if fits("large") and tiles("large") * batch >= 1024:
         return "large"
     for tier in ("medium", "large", "small"):
         if fits(tier):
@@ -297,6 +395,24 @@ BATCHED_THRESHOLDS_NOTE = (
     "not measured")
 
 
+# How choose_tier's ragged=True answers were arrived at.
+RAGGED_THRESHOLDS_NOTE = (
+    "a shape some tier divides keeps the tier of its tiled launch; any other "
+    "shape gets the single-launch tile-count thresholds applied to ceil tile "
+    "counts.  The thresholds are inherited, not fitted to ragged runs.  "
+    "measured (profiles/ragged.txt, MI355X, plain and fused no-inject), six "
+    "cells: 5001^3 (800 huge tiles) and 6145^3 (1225) -> huge, which is "
+    "6-20% ahead of large; 4097^3 and 4100^3 (561 huge tiles: a full round of 512 "
+    "resident workgroups plus a tail round of 49) -> huge, but large is "
+    "5-19% FASTER there: the ragged path has no stream-K to absorb the tail "
+    "round; skinny 8193x257x1025 -> tall, but medium is 24% faster (large "
+    "4-15%); small 1000x1000x333 -> medium, level with small plain and 9% "
+    "behind it fused, 29-41% ahead of large.  The choice is left as "
+    "specified; correcting the two losing cells needs a tail-round rule and "
+    "a skinny sweep that two shapes do not support.  Every other shape is "
+    "not measured")
+
+
 def sgemm_auto(a, b, c, alpha: float = 1.0, beta: float = 0.0):
     """Plain SGEMM with automatic tier selection; shapes no hand-written
     tier divides (e.g. M=100) fall back to the rocBLAS vendor path instead
@@ -310,21 +426,32 @@ def sgemm_auto(a, b, c, alpha: float = 1.0, beta: float = 0.0):
 
 
 def ft_sgemm_auto(a, b, c, alpha: float = 1.0, beta: float = 0.0,
-                  inject: bool = True, report: FaultReport | None = None):
-    """Fused-ABFT SGEMM with automatic tier selection.  Shapes no tier
-    divides fall back to the rocBLAS GEMM wrapped in the OFFLINE checksum
-    ABFT chain (kernel id 10 semantics: detection verdicts, no in-kernel
-    correction — the strongest FT available without a tile fit); a verdict
-    above the threshold raises, making silent corruption impossible on the
-    fallback path.
+                  inject: bool = True, report: FaultReport | None = None,
+                  misfit: str = "baseline"):
+    """Fused-ABFT SGEMM with automatic tier selection.  What happens to a
+    shape no tier divides is the caller's choice:
 
-    report: passed to ft_sgemm when a tier fits.  On the rocBLAS fallback
-    branch the report is left untouched: that branch has no in-kernel
-    locate/correct to report on, and it already raises on a tripped
-    verdict."""
+    misfit="baseline" (the default): the rocBLAS GEMM wrapped in the OFFLINE
+    checksum ABFT chain (kernel id 10 semantics: detection verdicts, no
+    in-kernel correction); a verdict above the threshold raises, making
+    silent corruption impossible on the fallback path.
+    misfit="ragged": ft_sgemm_ragged on choose_tier(..., ragged=True) — the
+    fused kernel's in-register locate/correct, injector self-test and fault
+    report, for any shape.
+
+    report: passed to ft_sgemm when a tier fits, and to ft_sgemm_ragged.  On
+    the rocBLAS fallback branch the report is left untouched: that branch
+    has no in-kernel locate/correct to report on, and it already raises on
+    a tripped verdict."""
+    if misfit not in ("baseline", "ragged"):
+        raise ValueError(f"ft_sgemm_auto: misfit must be 'baseline' or "
+                         f"'ragged', got {misfit!r}")
     k, m = a.shape
     n = b.shape[1]
     tier = choose_tier(m, n, k)
+    if tier is None and misfit == "ragged":
+        return ft_sgemm_ragged(choose_tier(m, n, k, ragged=True), a, b, c,
+                               alpha, beta, inject=inject, report=report)
     if tier is None:
         pk = k if k <= 1024 or k % 1024 else 1024
         _, (res_row, res_col) = baseline_ft(a, b, c, alpha, beta, panel_k=pk)

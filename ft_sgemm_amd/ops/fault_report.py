@@ -85,6 +85,12 @@ class FaultReport:
     Owns the two int32 device tensors the kernels write.  A report
     accumulates across launches until reset(); when more than `capacity`
     events arrive the extra ones are counted (read().dropped) but not kept.
+
+    Ragged launches (ops.ft_sgemm_ragged) compute on whole tiles whose
+    out-of-range part is zero padding.  A fault absorbed there is detected,
+    located and corrected like any other and its event carries its true
+    padded coordinates: i >= M or j >= N is possible, and k_end is a whole
+    number of panels and may exceed K.  Such an element is not part of C.
     """
 
     def __init__(self, capacity: int = 1024, device="cuda"):
@@ -163,7 +169,8 @@ class BatchedFaultReport:
 
 
 def predict_injected_events(tier: str, m: int, n: int, k: int,
-                            verify_windows: int = 20) -> List[FaultEvent]:
+                            verify_windows: int = 20,
+                            ragged: bool = False) -> List[FaultEvent]:
     """The exact events the classic fused kernel's injector must produce for
     an (m, n, k) GEMM on `tier`, sorted by (i, j, k_begin).
 
@@ -171,21 +178,30 @@ def predict_injected_events(tier: str, m: int, n: int, k: int,
     it) and csrc/ft_kernels.hpp (sgemm_mfma: victim rotation, MFMA
     accumulator layout): every block injects once per verify window w into
     acc[0][0][0] of thread (w * 67) % THREADS.
+
+    ragged: model ft_sgemm_ragged (csrc/ft_ragged.hpp) instead: any shape, a
+    ceil(m/bm) x ceil(n/bn) grid and ceil(k/bkf) panels, the same rule in
+    every block.  In an edge tile a victim can lie in the padding (i >= m
+    or j >= n), and the last window's k_end is a whole number of panels and
+    can exceed k: both are predicted as the kernel logs them.
     """
     t = TILING[tier]
     bm, bn, wm, wn = t["bm"], t["bn"], t["wm"], t["wn"]
     bkf = t.get("bkf", t["bk"])
     mm = 16 if t["mfma"] == "f32_16x16x4" else 32
-    if m % bm or n % bn or k % bkf:
+    if ragged:
+        if min(m, n, k) < 1:
+            raise ValueError(f"shape ({m}, {n}, {k}) is empty")
+    elif m % bm or n % bn or k % bkf:
         raise ValueError(f"shape ({m}, {n}, {k}) does not divide tier {tier}")
     nthreads = threads(tier)
     waves_n = bn // wn
-    niter = k // bkf
+    niter = -(-k // bkf)
     stride = max(1, niter // (verify_windows if verify_windows > 0 else 20))
     nwin = -(-niter // stride)
     out = []
-    for bx in range(m // bm):
-        for by in range(n // bn):
+    for bx in range(-(-m // bm)):
+        for by in range(-(-n // bn)):
             for w in range(nwin):
                 tid = (w * 67) % nthreads
                 wave, lane = tid >> 6, tid & 63
@@ -218,8 +234,8 @@ class InjectionModel(NamedTuple):
 
 
 def predict_injection_model(tier: str, m: int, n: int, k: int, tau: float,
-                            inj_mag: float,
-                            verify_windows: int = 20) -> InjectionModel:
+                            inj_mag: float, verify_windows: int = 20,
+                            ragged: bool = False) -> InjectionModel:
     """CPU model of inject -> verify -> locate -> correct in the classic
     fused kernel, from the same rotation rule as predict_injected_events.
 
@@ -232,17 +248,25 @@ def predict_injection_model(tier: str, m: int, n: int, k: int, tau: float,
     when that row lies in the wave tile; when no column exceeds tau the
     verify is counted as unlocated and the accumulators stay as they are.
     Roundoff (orders of magnitude below any tau in use) is not modelled.
+
+    ragged: model ft_sgemm_ragged: any shape, ceil grids and ceil(k/bkf)
+    panels.  The counts cover every block, padding victims included; mult
+    and residue are the (m, n) window of C, where padding never lands.
     """
     t = TILING[tier]
     bm, bn, wm, wn = t["bm"], t["bn"], t["wm"], t["wn"]
     bkf = t.get("bkf", t["bk"])
     mm = 16 if t["mfma"] == "f32_16x16x4" else 32
-    if m % bm or n % bn or k % bkf:
+    if ragged:
+        if min(m, n, k) < 1:
+            raise ValueError(f"shape ({m}, {n}, {k}) is empty")
+    elif m % bm or n % bn or k % bkf:
         raise ValueError(f"shape ({m}, {n}, {k}) does not divide tier {tier}")
     nthreads = threads(tier)
     nwaves = nthreads // 64
     waves_n = bn // wn
-    niter = k // bkf
+    niter = -(-k // bkf)
+    gx, gy = -(-m // bm), -(-n // bn)
     stride = max(1, niter // (verify_windows if verify_windows > 0 else 20))
     nwin = -(-niter // stride)
     tripped = corrected = uncorrected = unlocated = 0
@@ -288,11 +312,11 @@ def predict_injection_model(tier: str, m: int, n: int, k: int, tau: float,
         for c, r in pending[wv].items():
             for i, e in r.items():
                 bres[(wv // waves_n) * wm + i, (wv % waves_n) * wn + c] += e
-    nblk = (m // bm) * (n // bn)
-    mult = bmult.repeat(m // bm, n // bn)
-    residue = bres.repeat(m // bm, n // bn)
-    for bx in range(m // bm):
-        for by in range(n // bn):
+    nblk = gx * gy
+    mult = bmult.repeat(gx, gy)[:m, :n]
+    residue = bres.repeat(gx, gy)[:m, :n]
+    for bx in range(gx):
+        for by in range(gy):
             for wv in range(nwaves):
                 wave_totals[(bx, by, wv)] = wave_peak[wv]
             for (wv, c), v in col_peak.items():
