@@ -88,7 +88,8 @@ bool run_kernel(int kid, int M, int N, int K, const float* dA,
     }();
     float r0 = 0, r1 = 0;
     return ftsgemm::baseline_ft_sgemm(M, N, K, dA, dB, dC, alpha, beta, ws,
-                                      panel_k, &r0, &r1, 0) == 0;
+                                      panel_k, &r0, &r1, 0, /*fault=*/nullptr,
+                                      /*verdicts=*/nullptr) == 0;
   }
   // ids 0, 7, 8, 9: rocBLAS (reference falls back to cuBLAS, sgemm.cu:197)
   return ftsgemm::rocblas_sgemm_nt(M, N, K, dA, dB, dC, alpha, beta, 0) == 0;

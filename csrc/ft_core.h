@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
 #include "fault_log.h"
 
 namespace ftsgemm {
@@ -133,13 +135,36 @@ struct BaselineWorkspace {
 int rocblas_sgemm_nt(int M, int N, int K, const float* A, const float* B,
                      float* C, float alpha, float beta, hipStream_t stream);
 
+// Test seam of the baseline chain: one fault put into the running C right
+// after the GEMM of panel `panel`, before that panel's checksum update and
+// verdict.  C[i + j*M] += value, or = value when overwrite.
+struct BaselineFault {
+  int panel, i, j;
+  float value;
+  bool overwrite;
+};
+
+// One verdict of the baseline chain: the squared residual norms computed
+// after panel `panel`.
+struct BaselineVerdict {
+  int panel;
+  float res_row, res_col;
+};
+
 // Non-fused ABFT baseline: per 256-wide K panel, rocBLAS
 // sgemm + 6x sgemv + 2x saxpy + 2x sdot (call-chain parity with
 // baseline_ft_sgemm.cuh:3-32).  Returns 0 on success; verdicts (squared
-// residual norms) written to res_row/res_col (host pointers).
+// residual norms) written to res_row/res_col (host pointers): the worst
+// verified panel's, and NaN or Inf whenever any panel's was.
+// fault (nullptr = none) is the seam above; a fault outside
+// 0 <= panel < ceil(K / panel_k), 0 <= i < M, 0 <= j < N returns -2 before
+// anything is launched.  verdicts (nullptr = not wanted) receives every
+// verdict computed, in panel order.
 int baseline_ft_sgemm(int M, int N, int K, const float* A, const float* B,
                       float* C, float alpha, float beta,
                       const BaselineWorkspace& ws, int panel_k,
-                      float* res_row, float* res_col, hipStream_t stream);
+                      float* res_row, float* res_col, hipStream_t stream,
+                      const BaselineFault* fault,
+                      std::vector<BaselineVerdict>* verdicts);
 
 }  // namespace ftsgemm

@@ -18,12 +18,23 @@
 //             f32x4, wave+LDS reduce) instead of rocblas_sgemv: the
 //             per-panel full-C gemv sweeps dominated the measured 34.3%
 //             overhead in round 1.
-// FT_SGEMM_VERIFY_EVERY=j (default 1) runs the C-sweep + verdict every
+// FT_SGEMM_VERIFY_EVERY=j (default 2) runs the C-sweep + verdict every
 // j-th panel (and always on the last): the maintained operand checksums
 // still update EVERY panel, so a detected fault is located in time at a
 // j-panel granularity — the knob trades verdict latency for overhead
 // (VERDICT r01 allows per-j-panel verdicts; the reference verifies per
 // panel at T4 cost ratios).
+//
+// What detection is tested to guarantee (tests/test_gpu_baseline_detect.py,
+// through the BaselineFault seam): a single-element fault in C is seen by
+// BOTH verdicts at every shape class — f32x4 and scalar reductions, second
+// row band, ragged last column slice, 1x1 — as |fault|^2 within a derived
+// roundoff band, at the first verified panel at or after it, and survives
+// into the returned worst-panel pair.  A verdict that is NaN or Inf (a NaN
+// or Inf left in C) is returned as such: the worst-panel reduction used to
+// start from 0 and compare with >, which is false for NaN, so such a fault
+// came back as 0.0.  Callers raise at 9500^2 (ft_sgemm_auto), so a smaller
+// fault shows in the verdict but does not raise.
 
 #include <hip/hip_runtime.h>
 #include <rocblas/rocblas.h>
@@ -106,6 +117,21 @@ __global__ __launch_bounds__(256) void rowsum_kernel(
   }
 }
 
+// The fault seam (BaselineFault): one thread, one element of C.
+__global__ void baseline_fault_kernel(float* __restrict__ C, size_t idx,
+                                      float value, int overwrite) {
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    C[idx] = overwrite ? value : C[idx] + value;
+}
+
+// Worst of two verdicts, where a non-finite one is worse than any finite
+// one and a NaN, once seen, stays (v > worst is false for a NaN on either
+// side, which used to report a NaN verdict as 0.0, a perfect score).
+float worse_verdict(float worst, float v) {
+  if (worst != worst) return worst;
+  return (v <= worst) ? worst : v;
+}
+
 int env_int(const char* name, int dflt) {
   const char* e = std::getenv(name);
   return e ? std::atoi(e) : dflt;
@@ -144,7 +170,14 @@ int rocblas_sgemm_nt(int M, int N, int K, const float* A, const float* B,
 int baseline_ft_sgemm(int M, int N, int K, const float* A, const float* B,
                       float* C, float alpha, float beta,
                       const BaselineWorkspace& ws, int panel_k,
-                      float* res_row, float* res_col, hipStream_t stream) {
+                      float* res_row, float* res_col, hipStream_t stream,
+                      const BaselineFault* fault,
+                      std::vector<BaselineVerdict>* verdicts) {
+  if (panel_k < 1) return -2;
+  const int npanels = (K + panel_k - 1) / panel_k;
+  if (fault &&(fault->panel < 0 || fault->panel >= npanels || fault->i < 0 ||
+                fault->i >= M || fault->j < 0 || fault->j >= N))
+    return -2;  // before anything is launched
   rocblas_handle h = get_handle();
   RB_CHECK(rocblas_set_stream(h, stream));
   // Host pointer mode for the alpha/beta scalars; the per-panel dot
@@ -173,8 +206,8 @@ int baseline_ft_sgemm(int M, int N, int K, const float* A, const float* B,
   RB_CHECK(rocblas_sgemv(h, rocblas_operation_transpose, M, N, &beta, C, M,
                          ws.ones, 1, &zero, ws.ref_col, 1));
 
-  const int npanels = (K + panel_k - 1) / panel_k;
   int pv = 0;  // verdict slot counter (2 floats per verdict)
+  std::vector<int> vpanel;  // panel of each verdict slot
   for (int p = 0; p < npanels; ++p) {
     const int k0 = p * panel_k;
     const int kp = (K - k0 < panel_k) ? (K - k0) : panel_k;
@@ -187,6 +220,10 @@ int baseline_ft_sgemm(int M, int N, int K, const float* A, const float* B,
                            rocblas_operation_transpose, M, N, kp, &alpha, Ap,
                            M, Bp, N, &beta_run, C, M));
     roctxRangePop();
+    if (fault && fault->panel == p)
+      hipLaunchKernelGGL(baseline_fault_kernel, dim3(1), dim3(64), 0, stream,
+                         C, (size_t)fault->i + (size_t)fault->j * M,
+                         fault->value, fault->overwrite ? 1 : 0);
     roctxRangePush("baseline_checksum_update");
     // Panel operand sums: s_a = Ap^T e_M, s_b = Bp^T e_N
     if (chain) {
@@ -236,6 +273,7 @@ int baseline_ft_sgemm(int M, int N, int K, const float* A, const float* B,
         rocblas_sdot(h, N, ws.col_c, 1, ws.col_c, 1, ws.d_res + 2 * pv + 1));
     RB_CHECK(rocblas_set_pointer_mode(h, rocblas_pointer_mode_host));
     roctxRangePop();  // baseline_verify_verdict
+    vpanel.push_back(p);
     ++pv;
   }
   std::vector<float> res(2 * pv);
@@ -245,9 +283,12 @@ int baseline_ft_sgemm(int M, int N, int K, const float* A, const float* B,
     return -1;
   *res_row = 0.f;
   *res_col = 0.f;
+  if (verdicts) verdicts->clear();
   for (int v = 0; v < pv; ++v) {  // worst panel, not last
-    if (res[2 * v] > *res_row) *res_row = res[2 * v];
-    if (res[2 * v + 1] > *res_col) *res_col = res[2 * v + 1];
+    *res_row = worse_verdict(*res_row, res[2 * v]);
+    *res_col = worse_verdict(*res_col, res[2 * v + 1]);
+    if (verdicts)
+      verdicts->push_back({vpanel[v], res[2 * v], res[2 * v + 1]});
   }
   return 0;
 }

@@ -321,11 +321,19 @@ void rocblas_sgemm_nt(at::Tensor a, at::Tensor b, at::Tensor c, double alpha,
   TORCH_CHECK(st == 0, "rocblas_sgemm failed with status ", st);
 }
 
-std::tuple<double, double> baseline_ft(at::Tensor a, at::Tensor b,
-                                       at::Tensor c, double alpha,
-                                       double beta, int64_t panel_k) {
+// fault: the chain's test seam (ft_core.h BaselineFault) as (panel, i, j,
+// value, overwrite), validated here before anything is launched.  Returns
+// (res_row, res_col, [(panel, res_row, res_col) per verified panel]).
+using BaselineFaultArg =
+    std::tuple<int64_t, int64_t, int64_t, double, bool>;
+using BaselineVerdictRow = std::tuple<int64_t, double, double>;
+
+std::tuple<double, double, std::vector<BaselineVerdictRow>> baseline_ft(
+    at::Tensor a, at::Tensor b, at::Tensor c, double alpha, double beta,
+    int64_t panel_k, c10::optional<BaselineFaultArg> fault) {
   int64_t M, N, K;
   check_inputs(a, b, c, M, N, K);
+  TORCH_CHECK(panel_k >= 1, "baseline_ft: panel_k must be >= 1");
   auto opts = a.options();
   int64_t mx = std::max(M, N);
   at::Tensor ones = at::ones({mx}, opts);
@@ -341,14 +349,29 @@ std::tuple<double, double> baseline_ft(at::Tensor a, at::Tensor b,
       col_c.mutable_data_ptr<float>(),   s_a.mutable_data_ptr<float>(),
       s_b.mutable_data_ptr<float>(),     ref_row.mutable_data_ptr<float>(),
       ref_col.mutable_data_ptr<float>(), d_res.mutable_data_ptr<float>()};
+  ftsgemm::BaselineFault bf{};
+  if (fault.has_value()) {
+    const auto& [fp, fi, fj, fv, fo] = *fault;
+    TORCH_CHECK(fp >= 0 && fp < npanels, "baseline_ft: fault panel ", fp,
+                " outside [0, ", npanels, ")");
+    TORCH_CHECK(fi >= 0 && fi < M && fj >= 0 && fj < N,
+                "baseline_ft: fault site (", fi, ", ", fj, ") outside the ", M,
+                " x ", N, " result");
+    bf = {(int)fp, (int)fi, (int)fj, (float)fv, fo};
+  }
   float res_row = 0.f, res_col = 0.f;
+  std::vector<ftsgemm::BaselineVerdict> verdicts;
   auto stream = at::cuda::getCurrentCUDAStream();
   int st = ftsgemm::baseline_ft_sgemm(
       (int)M, (int)N, (int)K, a.const_data_ptr<float>(),
       b.const_data_ptr<float>(), c.mutable_data_ptr<float>(), (float)alpha,
-      (float)beta, ws, (int)panel_k, &res_row, &res_col, stream.stream());
+      (float)beta, ws, (int)panel_k, &res_row, &res_col, stream.stream(),
+      fault.has_value() ? &bf : nullptr, &verdicts);
   TORCH_CHECK(st == 0, "baseline_ft_sgemm failed with status ", st);
-  return {(double)res_row, (double)res_col};
+  std::vector<BaselineVerdictRow> rows;
+  for (const auto& v : verdicts)
+    rows.emplace_back((int64_t)v.panel, (double)v.res_row, (double)v.res_col);
+  return {(double)res_row, (double)res_col, rows};
 }
 
 bool tier_supported(int64_t tier, int64_t M, int64_t N, int64_t K) {
@@ -468,7 +491,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ragged_workspace_floats", &ragged_workspace_floats,
         "ABFT scratch floats a fused sgemm_ragged call allocates");
   m.def("rocblas_sgemm", &rocblas_sgemm_nt, "rocBLAS oracle SGEMM");
-  m.def("baseline_ft", &baseline_ft, "non-fused rocBLAS ABFT baseline");
+  m.def("baseline_ft", &baseline_ft, "non-fused rocBLAS ABFT baseline",
+        py::arg("a"), py::arg("b"), py::arg("c"), py::arg("alpha"),
+        py::arg("beta"), py::arg("panel_k"), py::arg("fault") = py::none());
   m.def("tier_supported", &tier_supported, "tile divisibility check");
   m.def("locate_selftest", &locate_selftest,
         "device self-test of the ABFT locate/correct");

@@ -8,6 +8,8 @@ implementation and the extension is not required.
 
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
 
@@ -265,10 +267,25 @@ def rocblas_sgemm(a, b, c, alpha: float = 1.0, beta: float = 0.0):
 
 
 def baseline_ft(a, b, c, alpha: float = 1.0, beta: float = 0.0,
-                panel_k: int = 1024):
-    """Kernel id 10: non-fused rocBLAS ABFT chain.  Returns (c, verdicts)."""
-    res = _require_ext().baseline_ft(a, b, c, alpha, beta, panel_k)
-    return c, res
+                panel_k: int = 1024, fault=None, per_panel: bool = False):
+    """Kernel id 10: non-fused rocBLAS ABFT chain.  Returns (c, (res_row,
+    res_col)): the squared residual norms of the worst verified panel, NaN
+    or Inf whenever any panel's was.
+
+    fault: test seam, (panel, i, j, value, overwrite) — after the GEMM of
+    K panel `panel` the element (i, j) of the M x N result (c[j, i]) gets
+    += value, or = value when overwrite.  Out-of-range indices raise before
+    anything is launched.
+    per_panel: also return every verdict computed, in order, as a third
+    item [(panel, res_row, res_col), ...]."""
+    if fault is not None:
+        p, i, j, value, overwrite = fault
+        fault = (int(p), int(i), int(j), float(value), bool(overwrite))
+    res_row, res_col, panels = _require_ext().baseline_ft(
+        a, b, c, alpha, beta, panel_k, fault)
+    if per_panel:
+        return c, (res_row, res_col), panels
+    return c, (res_row, res_col)
 
 
 def selftest_descriptors(rows):
@@ -433,8 +450,9 @@ def ft_sgemm_auto(a, b, c, alpha: float = 1.0, beta: float = 0.0,
 
     misfit="baseline" (the default): the rocBLAS GEMM wrapped in the OFFLINE
     checksum ABFT chain (kernel id 10 semantics: detection verdicts, no
-    in-kernel correction); a verdict above the threshold raises, making
-    silent corruption impossible on the fallback path.
+    in-kernel correction); a verdict above the threshold of ERR_BOUND^2, or
+    one that is NaN or Inf, raises, making silent corruption impossible on
+    the fallback path.
     misfit="ragged": ft_sgemm_ragged on choose_tier(..., ragged=True) — the
     fused kernel's in-register locate/correct, injector self-test and fault
     report, for any shape.
@@ -456,8 +474,12 @@ def ft_sgemm_auto(a, b, c, alpha: float = 1.0, beta: float = 0.0,
         pk = k if k <= 1024 or k % 1024 else 1024
         _, (res_row, res_col) = baseline_ft(a, b, c, alpha, beta, panel_k=pk)
         # Squared residual l2 norms; fault-free roundoff at these operand
-        # scales is orders of magnitude below ERR_BOUND^2.
-        if max(res_row, res_col) > ERR_BOUND * ERR_BOUND:
+        # scales is orders of magnitude below ERR_BOUND^2.  Clean means
+        # both finite and within it: a NaN verdict (a NaN left in C) fails
+        # every comparison, so the test is for clean, not for tripped.
+        limit = ERR_BOUND * ERR_BOUND
+        if not (math.isfinite(res_row) and math.isfinite(res_col) and
+                res_row <= limit and res_col <= limit):
             raise RuntimeError(
                 f"ft_sgemm_auto fallback: offline ABFT verdict tripped "
                 f"(res_row={res_row:.3e}, res_col={res_col:.3e}) — "

@@ -166,6 +166,44 @@ def abft_ratio_locate(prod: np.ndarray, a: np.ndarray, b: np.ndarray,
     return out.astype(np.float32), locs
 
 
+def baseline_ft_emulate(a, b, c0, alpha: float, beta: float, panel_k: int,
+                        verify_every: int = 2, fault=None):
+    """fp32 emulation of the device's offline checksum chain
+    (csrc/rocblas_path.hip baseline_ft_sgemm), step for step: the maintained
+    checksums start from beta * C0 and grow by alpha * Ap (Bp^T e) per K
+    panel, and every verify_every-th panel and the last compare them with
+    the sums of the running C.  a (M, K), b (N, K), c0 (M, N) numpy arrays;
+    fault = (panel, i, j, value, overwrite) as ops.baseline_ft takes it.
+    Only the order inside each sum is numpy's, not the device's.  Returns
+    (c, [(panel, r_row (M,), r_col (N,)) per verified panel]) with fp32
+    residual vectors; a verdict is the fp32 dot of one with itself."""
+    f32 = np.float32
+    a, b = a.astype(f32), b.astype(f32)
+    c = c0.astype(f32).copy()
+    al, be = f32(alpha), f32(beta)
+    k = a.shape[1]
+    ref_row = be * c.sum(axis=1, dtype=f32)
+    ref_col = be * c.sum(axis=0, dtype=f32)
+    npanels = -(-k // panel_k)
+    out = []
+    for p in range(npanels):
+        ap = a[:, p * panel_k:(p + 1) * panel_k]
+        bp = b[:, p * panel_k:(p + 1) * panel_k]
+        c = al * (ap @ bp.T) + (be if p == 0 else f32(1)) * c
+        if fault is not None and fault[0] == p:
+            _, i, j, value, overwrite = fault
+            c[i, j] = f32(value) if overwrite else c[i, j] + f32(value)
+        s_a = ap.sum(axis=0, dtype=f32)
+        s_b = bp.sum(axis=0, dtype=f32)
+        ref_row = ref_row + al * (ap @ s_b)
+        ref_col = ref_col + al * (bp @ s_a)
+        if (p + 1) % verify_every != 0 and p != npanels - 1:
+            continue
+        out.append((p, c.sum(axis=1, dtype=f32) - ref_row,
+                    c.sum(axis=0, dtype=f32) - ref_col))
+    return c, out
+
+
 def baseline_ft_check(a, b, panel_k: int = 256, tau: float = ERR_BOUND):
     """Non-fused baseline semantics (include/baseline_ft_sgemm.cuh:1-33):
     per 256-wide K panel, compare e^T(A@B^T) against (e^T A)@B^T and
