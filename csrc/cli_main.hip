@@ -72,7 +72,7 @@ bool run_kernel(int kid, int M, int N, int K, const float* dA,
   if (kid >= 11 && kid <= 16) {
     g.abft = true;
     g.inject = inject;
-    g.ws = abft_ws(ftsgemm::sgemm_abft_workspace_floats(kid - 11, M, N, K));
+    g.ws = abft_ws(ftsgemm::sgemm_abft_workspace_floats(kid - 11, g));
     g.log = log;
     return ftsgemm::sgemm_tier_launch(kid - 11, g) == hipSuccess;
   }

@@ -6,6 +6,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
+
 #include "ft_core.h"
 #include "generated/tile_params.h"
 
@@ -14,9 +16,7 @@ namespace ftsgemm {
 #define FT_DECL(name, BM, BN, BK, WM, WN, MM)              \
   hipError_t launch_tier_##name(const GemmArgs& g);         \
   hipError_t launch_tier_batched_##name(const GemmArgs& g); \
-  hipError_t launch_tier_ragged_##name(const GemmArgs& g);  \
-  size_t abft_ws_floats_##name(int M, int N, int K);        \
-  size_t abft_ws_floats_ragged_##name(int M, int N, int K);
+  hipError_t launch_tier_ragged_##name(const GemmArgs& g);
 FT_TIER_LIST(FT_DECL)
 #undef FT_DECL
 
@@ -28,15 +28,12 @@ struct TierRow {
   hipError_t (*launch)(const GemmArgs&);
   hipError_t (*launch_batched)(const GemmArgs&);  // batch > 1
   hipError_t (*launch_ragged)(const GemmArgs&);   // g.ragged
-  size_t (*ws_floats)(int, int, int);
-  size_t (*ws_floats_ragged)(int, int, int);
-  int bm, bn, bk;
+  int bm, bn, bk, wm;
 };
 const TierRow kTiers[FT_N_TIERS] = {
-#define FT_ROW(name, BM, BN, BK, WM, WN, MM)                   \
-  {launch_tier_##name,    launch_tier_batched_##name,           \
-   launch_tier_ragged_##name, abft_ws_floats_##name,            \
-   abft_ws_floats_ragged_##name, BM, BN, BK},
+#define FT_ROW(name, BM, BN, BK, WM, WN, MM)                             \
+  {launch_tier_##name, launch_tier_batched_##name, launch_tier_ragged_##name, \
+   BM, BN, BK, WM},
     FT_TIER_LIST(FT_ROW)
 #undef FT_ROW
 };
@@ -47,40 +44,65 @@ const TierRow* tier_row(int tier) {
 
 }  // namespace
 
-hipError_t sgemm_tier_launch(int tier, const GemmArgs& g) {
-  const TierRow* t = tier_row(tier);
-  if (!t || g.batch < 1) return hipErrorInvalidValue;
-  if (g.ragged) {
-    // one product only; a leading dimension may pad its rows, never cut them
-    if (g.batch > 1) return hipErrorInvalidValue;
-    if ((g.lda && g.lda < g.M) || (g.ldb && g.ldb < g.N) ||
-        (g.ldc && g.ldc < g.M))
-      return hipErrorInvalidValue;
-    return t->launch_ragged(g);
-  }
-  return g.batch > 1 ? t->launch_batched(g) : t->launch(g);
-}
-
-size_t sgemm_abft_workspace_floats_ragged(int tier, int M, int N, int K) {
-  const TierRow* t = tier_row(tier);
-  return t && M > 0 && N > 0 && K > 0 ? t->ws_floats_ragged(M, N, K) : 0;
-}
-
-// Workspace floats needed by the fused-ABFT path of a tier (the segment-sum
-// matrix SA).
-size_t sgemm_abft_workspace_floats(int tier, int M, int N, int K) {
-  const TierRow* t = tier_row(tier);
-  return t ? t->ws_floats(M, N, K) : 0;
-}
-
-size_t sgemm_abft_workspace_floats_batched(int tier, int M, int N, int K,
-                                           int nA) {
-  return (nA > 0 ? (size_t)nA : 0) * sgemm_abft_workspace_floats(tier, M, N, K);
-}
-
+// K is tested against the plain kernel's panel depth: every tier's fused
+// depth bkf divides its bk (kernel_table.py), so the fused twin's whole
+// panels follow.  M, N % 4: the f32x4 epilogue.
 bool sgemm_tier_supported(int tier, int M, int N, int K) {
   const TierRow* t = tier_row(tier);
   return t && !(M % t->bm || N % t->bn || K % t->bk || M % 4 || N % 4);
+}
+
+// Every rule a launcher relies on; the launch_tier* templates check nothing
+// themselves and are reachable only through sgemm_tier_launch.  (Stream-K's
+// hipErrorNotSupported gates are a choice between two legal launches, not a
+// rule, and stay in its launcher.)
+const char* gemm_args_error(int tier, const GemmArgs& g) {
+  constexpr int kMaxGridYZ = 65535;  // gridDim.y and .z
+  const TierRow* t = tier_row(tier);
+  if (!t) return "unknown tier id";
+  if (g.M < 1 || g.N < 1 || g.K < 1) return "M, N and K must be >= 1";
+  if (g.abft && !g.ws) return "a fused-ABFT launch needs its workspace ws";
+  const uintptr_t ptrs =
+      (uintptr_t)g.A | (uintptr_t)g.B | (uintptr_t)g.C | (uintptr_t)g.ws;
+  if (g.ragged) {
+    if (g.batch != 1) return "a ragged launch is one product (batch == 1)";
+    // a leading dimension may pad its rows, never cut them
+    if ((g.lda && g.lda < g.M) || (g.ldb && g.ldb < g.N) ||
+        (g.ldc && g.ldc < g.M))
+      return "a leading dimension is shorter than its rows";
+    if (ptrs & 3) return "A, B, C and ws must be 4-byte aligned";
+    if ((g.N + t->bn - 1) / t->bn > kMaxGridYZ)
+      return "N needs more than 65535 tile columns";
+    return nullptr;
+  }
+  if (!sgemm_tier_supported(tier, g.M, g.N, g.K))
+    return "the tier requires M,N,K multiples of its tile (M,N of 4 as well)";
+  if (g.batch < 1 || g.batch > kMaxGridYZ) return "batch outside 1..65535";
+  if (g.batch > 1) {
+    // blockIdx.z carries the entry; 16-B staging and the f32x4 epilogue need
+    // every entry's base 16-B aligned
+    if (g.strideA < 0 || g.strideB < 0 || g.strideA % 4 || g.strideB % 4 ||
+        g.strideC % 4)
+      return "batch strides must be multiples of 4 floats, A's and B's >= 0";
+    if (g.strideC < (long long)g.M * g.N)
+      return "C entries must not overlap (strideC >= M*N)";
+    if (ptrs & 15) return "A, B, C and ws must be 16-byte aligned";
+  }
+  return nullptr;
+}
+
+hipError_t sgemm_tier_launch(int tier, const GemmArgs& g) {
+  if (gemm_args_error(tier, g)) return hipErrorInvalidValue;
+  const TierRow& t = kTiers[tier];
+  if (g.ragged) return t.launch_ragged(g);
+  return g.batch > 1 ? t.launch_batched(g) : t.launch(g);
+}
+
+size_t sgemm_abft_workspace_floats(int tier, const GemmArgs& g) {
+  const TierRow* t = tier_row(tier);
+  if (!t || g.M < 1 || g.N < 1 || g.K < 1) return 0;
+  const size_t nA = g.batch > 1 && g.strideA != 0 ? g.batch : 1;
+  return nA * 2 * (size_t)((g.M + t->wm - 1) / t->wm) * abft_sstr(g.K);
 }
 
 }  // namespace ftsgemm

@@ -14,8 +14,8 @@ namespace ftsgemm {
 // kernel argument): C = alpha*A*B^T + beta*C, column-major.  abft selects
 // the fused-ABFT twin, inject the always-on fault injector.
 // When abft, `ws` must point to a device scratch buffer of
-// sgemm_abft_workspace_floats(tier, M, N, K) fp32 elements (the launcher
-// fills it with the segment checksums of A before the fused kernel).
+// sgemm_abft_workspace_floats(tier, g) fp32 elements (the launcher fills it
+// with the segment checksums of A before the fused kernel).
 // `log` (optional, fused variants only) attaches a caller-owned fault log
 // (fault_log.h): the kernels' locate/correct path adds to its counters and
 // appends one event per detected fault.  The launch neither zeroes,
@@ -24,24 +24,23 @@ namespace ftsgemm {
 //
 // batch > 1 is a strided batch: for b in [0, batch), C_b = alpha * A_b *
 // B_b^T + beta * C_b with X_b = X + b * strideX, strides in floats.  strideA
-// and strideB may be 0 (one operand shared by every entry); strideC must be
-// >= M*N; every stride must be a multiple of 4 floats and A, B, C and ws
-// 16-byte aligned; batch <= 65535.  ws then holds
-// sgemm_abft_workspace_floats_batched(tier, M, N, K, nA) floats, nA = 1 for
-// a shared A (strideA == 0) and batch otherwise, and `log` points at the
-// first of `batch` logs laid out as counters[batch][FLOG_N_COUNTERS] and
+// and strideB may be 0 (one operand shared by every entry; a shared A is
+// encoded once, so ws then holds one matrix's checksums, not batch of them).
+// `log` points at the first of `batch` logs laid out as
+// counters[batch][FLOG_N_COUNTERS] and
 // events[batch][capacity][FLOG_EVENT_DWORDS]: entry b reports into log b.
 // A batched launch always takes the classic tile-per-workgroup path
-// (FT_SGEMM_STREAMK has no effect on it); batch == 1 is today's launch and
+// (FT_SGEMM_STREAMK has no effect on it); batch == 1 is the single launch and
 // ignores the strides.
 //
-// ragged lifts the shape and layout rules of a single product: any
-// M, N, K >= 1, A with leading dimension lda >= M, B with ldb >= N, C with
-// ldc >= M (0 = packed), base pointers with only fp32 alignment.  The ragged
-// twin of the classic kernel runs (ft_ragged.hpp) on ceil tile counts; ws then
-// holds sgemm_abft_workspace_floats_ragged(tier, M, N, K) floats.  ragged
-// with batch > 1 is rejected.  A fault injected into an edge tile's padding
-// is logged with its padded coordinates (fault_log.h).
+// ragged lifts the tile fit of a single product: any M, N, K >= 1, leading
+// dimensions lda / ldb / ldc (0 = packed), base pointers with only fp32
+// alignment.  The ragged twin of the classic kernel runs (ft_ragged.hpp) on
+// ceil tile counts.  A fault injected into an edge tile's padding is logged
+// with its padded coordinates (fault_log.h).
+//
+// Which shapes, strides, leading dimensions and alignments each of the three
+// forms accepts is stated once, in gemm_args_error.
 struct GemmArgs {
   bool abft, inject;
   int M, N, K;
@@ -58,19 +57,30 @@ struct GemmArgs {
   int lda = 0, ldb = 0, ldc = 0;  // ragged only; 0 = packed
 };
 
-// Launch tier `tier` (id per generated/tile_params.h).
+// The launch rules: nullptr when sgemm_tier_launch(tier, g) may launch g,
+// otherwise a static message naming the rule g breaks (tier id per
+// generated/tile_params.h).
+const char* gemm_args_error(int tier, const GemmArgs& g);
+
+// Launch tier `tier`; hipErrorInvalidValue, with nothing launched, when
+// gemm_args_error(tier, g) has a message.
 hipError_t sgemm_tier_launch(int tier, const GemmArgs& g);
 
+// The tile fit of a tiled (non-ragged) launch alone.
 bool sgemm_tier_supported(int tier, int M, int N, int K);
 
-size_t sgemm_abft_workspace_floats(int tier, int M, int N, int K);
+// Row stride of the ABFT workspace: round_up(K, 64), so the fused kernel's
+// 64-k strip loads never cross rows.
+inline int abft_sstr(int K) { return (K + 63) & ~63; }
 
-// nA consecutive copies of the per-matrix workspace (GemmArgs note).
-size_t sgemm_abft_workspace_floats_batched(int tier, int M, int N, int K,
-                                           int nA);
-
-// Workspace of a fused ragged launch: 2 * ceil(M/WM) * round_up(K, 64).
-size_t sgemm_abft_workspace_floats_ragged(int tier, int M, int N, int K);
+// Floats of g.ws a fused launch of g needs (g.ws itself is not looked at; 0
+// for an unknown tier or an empty shape).  Layout: one row per WM-row band of
+// A, ceil(M / WM) of them (a tiled M is a multiple of WM), each of
+// 2 * abft_sstr(K) floats holding the (plain, row-weighted) segment-sum
+// pairs INTERLEAVED at [2k], [2k+1]; a batch whose entries have their own A
+// (batch > 1, strideA != 0) holds `batch` consecutive copies.  B-side sums
+// are not needed by the ratio-locate scheme.
+size_t sgemm_abft_workspace_floats(int tier, const GemmArgs& g);
 
 // Device self-test of the fused kernels' shared detect / locate / correct
 // (locate_selftest.hip): one single-wave block per case plants up to two

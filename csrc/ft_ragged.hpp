@@ -312,26 +312,16 @@ __global__ __launch_bounds__(
     }
 }
 
-// Floats of segment-sum workspace of a fused ragged launch: one row of
-// 2 * sstr per WM-row band of A, the last band partial.
-template <int WM>
-size_t abft_workspace_floats_ragged_t(int M, int K) {
-  return 2 * (size_t)((M + WM - 1) / WM) * abft_sstr(K);
-}
-
 // Ragged launch of one tier: any M, N, K >= 1 on a ceil(M/BM) x ceil(N/BN)
 // grid of sgemm_mfma_ragged.  g.lda / ldb / ldc of 0 mean packed (M, N, M).
+// The workspace has one row per WM-row band of A, the last band partial.
 // No allocation and no sync, so the launch can be captured.
 template <int BM, int BN, int BK, int BKF, int WM, int WN, int MM>
 hipError_t launch_tier_ragged(const GemmArgs& g) {
   const bool abft = g.abft, inject = g.inject;
   const int M = g.M, N = g.N, K = g.K;
-  if (M < 1 || N < 1 || K < 1 || g.batch != 1) return hipErrorInvalidValue;
   const int lda = g.lda ? g.lda : M, ldb = g.ldb ? g.ldb : N,
             ldc = g.ldc ? g.ldc : M;
-  if (lda < M || ldb < N || ldc < M) return hipErrorInvalidValue;
-  if (((uintptr_t)g.A | (uintptr_t)g.B | (uintptr_t)g.C | (uintptr_t)g.ws) & 3)
-    return hipErrorInvalidValue;
   const auto fast_ok = [](const void* p, int ld) {
     return ((uintptr_t)p & 15) == 0 && ld % 4 == 0;
   };
@@ -339,15 +329,12 @@ hipError_t launch_tier_ragged(const GemmArgs& g) {
                    (fast_ok(g.B, ldb) ? RAGGED_FAST_B : 0) |
                    (fast_ok(g.C, ldc) ? RAGGED_FAST_C : 0);
   const int bk_used = abft ? BKF : BK;
-  const int gx = (M + BM - 1) / BM, gy = (N + BN - 1) / BN;
-  if (gy > 65535) return hipErrorInvalidValue;
-  dim3 grid(gx, gy);
+  dim3 grid((M + BM - 1) / BM, (N + BN - 1) / BN);
   dim3 block(tile_geom<BM, BN, BK, WM, WN, MM, false>::THREADS);
   const int stride = window_stride((K + bk_used - 1) / bk_used,
                                    abft ? g.verify_windows : 1);
   Checksums cs;
   if (abft) {
-    if (!g.ws) return hipErrorInvalidValue;
     cs.sstr = abft_sstr(K);
     cs.SA = g.ws;
     RoctxRange rr("abft_encode_segsum_ragged");

@@ -38,20 +38,12 @@ inline int streamk_env_mode() {
   return e ? std::atoi(e) : 2;
 }
 
-// ABFT workspace layout: (M/WM) rows, one per WM-band of A, each of
-// 2 * sstr floats holding the (plain, row-weighted) segment-sum pairs
-// INTERLEAVED at [2k], [2k+1]; sstr = round_up(K, 64) so the fused
-// kernel's 64-k strip loads never cross rows.  B-side sums are not needed
-// by the ratio-locate scheme.
-inline int abft_sstr(int K) { return (K + 63) & ~63; }
+// The launchers below check none of the launch rules: sgemm_tier_launch runs
+// gemm_args_error (dispatch.hip) first and is the only way in.
 
-template <int WM, int WN>
-size_t abft_workspace_floats_t(int M, int N, int K) {
-  return 2 * (size_t)(M / WM) * abft_sstr(K);
-}
-
-// The checksum operand of a fused kernel: SA and the row stride sstr it is
-// read with; both zero for a plain kernel.
+// The checksum operand of a fused kernel: SA (g.ws, layout at
+// sgemm_abft_workspace_floats) and the row stride sstr it is read with; both
+// zero for a plain kernel.
 struct Checksums {
   const float* SA = nullptr;
   int sstr = 0;
@@ -62,15 +54,13 @@ struct Checksums {
 // operand, ~1-2% of the GEMM at N=4096 (vs -11.6% for the in-kernel
 // cooperative sums pass this replaces — tools/probe_ablate.hip).
 template <int WM>
-hipError_t abft_encode(const GemmArgs& g, Checksums& cs) {
-  if (!g.abft) return hipSuccess;
-  if (!g.ws) return hipErrorInvalidValue;
+void abft_encode(const GemmArgs& g, Checksums& cs) {
+  if (!g.abft) return;
   cs.sstr = abft_sstr(g.K);
   cs.SA = g.ws;
   RoctxRange rr("abft_encode_segsum");
   hipLaunchKernelGGL((segsum_kernel<WM>), dim3(g.K), dim3(256), 0, g.stream,
                      g.M, g.K, cs.sstr, g.A, g.ws);
-  return hipSuccess;
 }
 
 // Inject+verify cadence: `steps` K-steps of a tile (classic: K / BK panels,
@@ -205,7 +195,7 @@ hipError_t launch_tier_streamk_t(const GemmArgs& g) {
   if (cap != hipStreamCaptureStatusNone) return hipErrorNotSupported;
 
   Checksums cs;
-  if (hipError_t e = abft_encode<WM>(g, cs); e != hipSuccess) return e;
+  abft_encode<WM>(g, cs);
   RoctxRange rr_main(abft ? (inject ? "ft_sgemm_streamk_abft_inject"
                                     : "ft_sgemm_streamk_abft")
                           : "sgemm_streamk_plain");
@@ -254,86 +244,57 @@ hipError_t launch_tier_streamk_t(const GemmArgs& g) {
 // BKF: K-panel depth of the fused-ABFT twin (may be smaller than the
 // plain BK so the +1KB/wave checksum strips don't push the block over an
 // LDS-occupancy boundary — kernel_table.py bkf note).
-template <int BM, int BN, int BK, int BKF, int WM, int WN, int MM>
+//
+// BATCHED (g.batch > 1, instantiated in the tier's _batched translation unit
+// only): g.batch GEMMs on a (M/BM, N/BN, batch) grid of the kernel's BATCHED
+// twin, entry b on A + b*strideA, B + b*strideB, C + b*strideC.  strideA == 0
+// shares A: its segment sums are then encoded once and read by every entry;
+// otherwise g.ws holds one copy of the per-matrix workspace layout per entry.
+// With a log attached, g.log is the first of g.batch logs (ft_core.h).
+// Always the classic decomposition: there is no batched stream-K, and
+// FT_SGEMM_STREAMK is not consulted.  No allocation and no sync on either
+// path, so the launch can be captured.
+template <int BM, int BN, int BK, int BKF, int WM, int WN, int MM,
+          bool BATCHED>
 hipError_t launch_tier(const GemmArgs& g) {
   const bool abft = g.abft, inject = g.inject;
   const int M = g.M, N = g.N, K = g.K;
   const int bk_used = abft ? BKF : BK;
-  if (M % BM || N % BN || K % bk_used || M % 4 || N % 4)
-    return hipErrorInvalidValue;
-  dim3 grid(M / BM, N / BN);
+  dim3 grid(M / BM, N / BN, BATCHED ? g.batch : 1);
   dim3 block(tile_geom<BM, BN, BK, WM, WN, MM, false>::THREADS);
   // whole bk_used panels; a plain kernel runs them all in one burst
   const int stride = window_stride(K / bk_used, abft ? g.verify_windows : 1);
+  BatchStrides bs;
   Checksums cs;
-  if (hipError_t e = abft_encode<WM>(g, cs); e != hipSuccess) return e;
-  RoctxRange rr_main(abft ? (inject ? "ft_sgemm_abft_inject" : "ft_sgemm_abft")
-                          : "sgemm_plain");
-  const FaultLog flog = attached_log(abft, g.log);
-  const auto kfn = select_variant(
-      abft, inject, flog.counters != nullptr,
-      &sgemm_mfma<BM, BN, BK, WM, WN, MM, false, false>,
-      [](auto inj, auto lg) {
-        return &sgemm_mfma<BM, BN, BKF, WM, WN, MM, true, decltype(inj)::value,
-                           2, decltype(lg)::value>;
-      });
-  hipLaunchKernelGGL(kfn, grid, block, 0, g.stream, M, N, K, g.A, g.B, g.C,
-                     g.alpha, g.beta, stride, stride, g.tau, g.inj_mag, cs.SA,
-                     cs.sstr, flog, BatchStrides{});
-  return hipGetLastError();
-}
-
-// Strided-batched launch of one tier: g.batch GEMMs on a (M/BM, N/BN, batch)
-// grid of the classic kernel's BATCHED twin, entry b on A + b*strideA,
-// B + b*strideB, C + b*strideC.  strideA == 0 shares A: its segment sums are
-// then encoded once and read by every entry; otherwise g.ws holds one copy of
-// the per-matrix workspace layout per entry.  With a log attached, g.log is
-// the first of g.batch logs (ft_core.h).  Always the classic decomposition:
-// there is no batched stream-K, and FT_SGEMM_STREAMK is not consulted.  No
-// allocation and no sync, so the launch can be captured.
-template <int BM, int BN, int BK, int BKF, int WM, int WN, int MM>
-hipError_t launch_tier_batched(const GemmArgs& g) {
-  const bool abft = g.abft, inject = g.inject;
-  const int M = g.M, N = g.N, K = g.K;
-  const int bk_used = abft ? BKF : BK;
-  if (M % BM || N % BN || K % bk_used || M % 4 || N % 4)
-    return hipErrorInvalidValue;
-  // blockIdx.z carries the entry; 16-B staging and the f32x4 epilogue need
-  // every entry's base 16-B aligned
-  if (g.batch < 1 || g.batch > 65535) return hipErrorInvalidValue;
-  if (g.strideA < 0 || g.strideB < 0 || g.strideA % 4 || g.strideB % 4 ||
-      g.strideC % 4 || g.strideC < (long long)M * N)
-    return hipErrorInvalidValue;
-  if (((uintptr_t)g.A | (uintptr_t)g.B | (uintptr_t)g.C | (uintptr_t)g.ws) &
-      15)
-    return hipErrorInvalidValue;
-  dim3 grid(M / BM, N / BN, g.batch);
-  dim3 block(tile_geom<BM, BN, BK, WM, WN, MM, false>::THREADS);
-  const int stride = window_stride(K / bk_used, abft ? g.verify_windows : 1);
-  BatchStrides bs{g.strideA, g.strideB, g.strideC, 0};
-  Checksums cs;
-  if (abft) {
-    if (!g.ws) return hipErrorInvalidValue;
-    const int nA = g.strideA == 0 ? 1 : g.batch;
-    const long long ws_each =
-        (long long)abft_workspace_floats_t<WM, WN>(M, N, K);
-    bs.SA = nA == 1 ? 0 : ws_each;
-    cs.sstr = abft_sstr(K);
-    cs.SA = g.ws;
-    RoctxRange rr("abft_encode_segsum_batched");
-    hipLaunchKernelGGL((segsum_batched_kernel<WM>), dim3(K, nA), dim3(256), 0,
-                       g.stream, M, K, cs.sstr, g.A, g.ws, g.strideA, ws_each);
+  if constexpr (!BATCHED) {
+    abft_encode<WM>(g, cs);
+  } else {
+    bs = {g.strideA, g.strideB, g.strideC, 0};
+    if (abft) {
+      const int nA = g.strideA == 0 ? 1 : g.batch;
+      cs.sstr = abft_sstr(K);
+      cs.SA = g.ws;
+      // one matrix's rows of the workspace (sgemm_abft_workspace_floats)
+      const long long ws_each = 2LL * (M / WM) * cs.sstr;
+      bs.SA = nA == 1 ? 0 : ws_each;
+      RoctxRange rr("abft_encode_segsum_batched");
+      hipLaunchKernelGGL((segsum_batched_kernel<WM>), dim3(K, nA), dim3(256),
+                         0, g.stream, M, K, cs.sstr, g.A, g.ws, g.strideA,
+                         ws_each);
+    }
   }
-  RoctxRange rr_main(abft ? (inject ? "ft_sgemm_batched_abft_inject"
-                                    : "ft_sgemm_batched_abft")
-                          : "sgemm_batched_plain");
+  RoctxRange rr_main(
+      abft ? (inject ? (BATCHED ? "ft_sgemm_batched_abft_inject"
+                                : "ft_sgemm_abft_inject")
+                     : (BATCHED ? "ft_sgemm_batched_abft" : "ft_sgemm_abft"))
+           : (BATCHED ? "sgemm_batched_plain" : "sgemm_plain"));
   const FaultLog flog = attached_log(abft, g.log);
   const auto kfn = select_variant(
       abft, inject, flog.counters != nullptr,
-      &sgemm_mfma<BM, BN, BK, WM, WN, MM, false, false, 2, false, true>,
+      &sgemm_mfma<BM, BN, BK, WM, WN, MM, false, false, 2, false, BATCHED>,
       [](auto inj, auto lg) {
         return &sgemm_mfma<BM, BN, BKF, WM, WN, MM, true, decltype(inj)::value,
-                           2, decltype(lg)::value, true>;
+                           2, decltype(lg)::value, BATCHED>;
       });
   hipLaunchKernelGGL(kfn, grid, block, 0, g.stream, M, N, K, g.A, g.B, g.C,
                      g.alpha, g.beta, stride, stride, g.tau, g.inj_mag, cs.SA,

@@ -30,8 +30,88 @@ void check_inputs(const at::Tensor& a, const at::Tensor& b,
               "ft_sgemm: C must be (N,M) for column-major MxN");
 }
 
-// counters / events: optional fault log of the fused kernels (fault_log.h),
-// int32, contiguous, on the operands' device; events is (capacity, 8).
+// The optional fault log of the fused kernels (fault_log.h) as a binding
+// takes it: int32, contiguous, on the operands' device `dev`, both tensors or
+// neither.  batch == 0 is an unbatched entry (sgemm, sgemm_ragged), batch >= 1
+// the batched one, and the two do not accept the same sets:
+//   unbatched  counters 1-D, FLOG_N_COUNTERS or more; events (capacity, 8),
+//              a capacity of 0 included;
+//   batched    counters exactly (batch, FLOG_N_COUNTERS); events
+//              (batch, capacity, 8), capacity >= 1.
+ftsgemm::FaultLog attach_fault_log(const char* nm, bool abft, at::Device dev,
+                                   const c10::optional<at::Tensor>& counters,
+                                   const c10::optional<at::Tensor>& events,
+                                   int64_t batch) {
+  TORCH_CHECK(counters.has_value() == events.has_value(), nm,
+              ": fault-log counters and events go together");
+  ftsgemm::FaultLog flog;
+  if (!counters.has_value()) return flog;
+  const at::Tensor& cn = *counters;
+  const at::Tensor& ev = *events;
+  const int64_t nc = ftsgemm::FLOG_N_COUNTERS, dw = ftsgemm::FLOG_EVENT_DWORDS;
+  TORCH_CHECK(abft, nm, ": a fault log needs a fused-ABFT kernel");
+  TORCH_CHECK(cn.scalar_type() == at::kInt && ev.scalar_type() == at::kInt,
+              nm, ": fault-log tensors must be int32");
+  TORCH_CHECK(cn.is_contiguous() && ev.is_contiguous(), nm,
+              ": fault-log tensors must be contiguous");
+  TORCH_CHECK(cn.device() == dev && ev.device() == dev, nm,
+              ": fault-log tensors must be on the operands' device");
+  if (batch == 0) {
+    TORCH_CHECK(cn.dim() == 1 && cn.size(0) >= nc, nm,
+                ": fault-log counters must hold ", nc, " int32");
+    TORCH_CHECK(ev.dim() == 2 && ev.size(1) == dw && ev.size(0) <= (1 << 24),
+                nm, ": fault-log events must be (capacity, ", dw, ") int32");
+  } else {
+    TORCH_CHECK(cn.dim() == 2 && cn.size(0) == batch && cn.size(1) == nc, nm,
+                ": fault-log counters must be (batch, ", nc, ") int32");
+    TORCH_CHECK(ev.dim() == 3 && ev.size(0) == batch && ev.size(2) == dw &&
+                    ev.size(1) >= 1 && ev.size(1) <= (1 << 24),
+                nm, ": fault-log events must be (batch, capacity, ", dw,
+                ") int32");
+  }
+  flog.counters = cn.mutable_data_ptr<int>();
+  flog.events = ev.mutable_data_ptr<int>();
+  flog.capacity = (int)ev.size(-2);
+  return flog;
+}
+
+// The one body behind sgemm, sgemm_batched and sgemm_ragged.  `g` arrives
+// with the layout its entry read off the tensors (M, N, K and the batch or
+// ragged fields); this fills in the rest, attaches the fault log (log_batch
+// as attach_fault_log's batch), holds the call to the launch rules
+// (gemm_args_error, the only statement of them on this side), allocates the
+// segment-checksum scratch and launches on the current stream.
+void launch_gemm(const char* nm, int64_t tier, ftsgemm::GemmArgs g, bool abft,
+                 bool inject, const at::Tensor& a, const at::Tensor& b,
+                 at::Tensor& c, double alpha, double beta, double tau,
+                 double inj_mag, int64_t verify_windows,
+                 const c10::optional<at::Tensor>& counters,
+                 const c10::optional<at::Tensor>& events, int64_t log_batch) {
+  const ftsgemm::FaultLog flog =
+      attach_fault_log(nm, abft, a.device(), counters, events, log_batch);
+  g.abft = abft, g.inject = inject;
+  g.A = a.const_data_ptr<float>(), g.B = b.const_data_ptr<float>();
+  g.C = c.mutable_data_ptr<float>();
+  g.alpha = (float)alpha, g.beta = (float)beta;
+  g.tau = (float)tau, g.inj_mag = (float)inj_mag;
+  g.verify_windows = (int)verify_windows;
+  g.stream = at::cuda::getCurrentCUDAStream().stream();
+  g.log = flog.counters ? &flog : nullptr;
+  at::Tensor ws;  // via the caching allocator; empty() launches nothing
+  if (abft) {
+    const size_t n = ftsgemm::sgemm_abft_workspace_floats((int)tier, g);
+    ws = at::empty({(int64_t)n}, a.options());
+    g.ws = ws.mutable_data_ptr<float>();
+  }
+  const char* broken = ftsgemm::gemm_args_error((int)tier, g);
+  TORCH_CHECK(!broken, nm, ": ", broken, " (tier ", tier, ", M=", g.M,
+              " N=", g.N, " K=", g.K, ")");
+  hipError_t err = ftsgemm::sgemm_tier_launch((int)tier, g);
+  TORCH_CHECK(err == hipSuccess, nm,
+              " launch failed: ", hipGetErrorString(err));
+}
+
+// counters / events: optional fault log (attach_fault_log, unbatched form).
 void sgemm(int64_t tier, bool abft, bool inject, at::Tensor a, at::Tensor b,
            at::Tensor c, double alpha, double beta, double tau,
            double inj_mag, int64_t verify_windows,
@@ -39,63 +119,21 @@ void sgemm(int64_t tier, bool abft, bool inject, at::Tensor a, at::Tensor b,
            c10::optional<at::Tensor> events) {
   int64_t M, N, K;
   check_inputs(a, b, c, M, N, K);
-  TORCH_CHECK(counters.has_value() == events.has_value(),
-              "ft_sgemm: fault-log counters and events go together");
-  ftsgemm::FaultLog flog;
-  if (counters.has_value()) {
-    const at::Tensor& cn = *counters;
-    const at::Tensor& ev = *events;
-    TORCH_CHECK(abft, "ft_sgemm: a fault log needs a fused-ABFT kernel");
-    TORCH_CHECK(cn.scalar_type() == at::kInt && ev.scalar_type() == at::kInt,
-                "ft_sgemm: fault-log tensors must be int32");
-    TORCH_CHECK(cn.is_contiguous() && ev.is_contiguous(),
-                "ft_sgemm: fault-log tensors must be contiguous");
-    TORCH_CHECK(cn.device() == a.device() && ev.device() == a.device(),
-                "ft_sgemm: fault-log tensors must be on the operands' device");
-    TORCH_CHECK(cn.dim() == 1 && cn.size(0) >= ftsgemm::FLOG_N_COUNTERS,
-                "ft_sgemm: fault-log counters must hold ",
-                (int)ftsgemm::FLOG_N_COUNTERS, " int32");
-    TORCH_CHECK(ev.dim() == 2 && ev.size(1) == ftsgemm::FLOG_EVENT_DWORDS &&
-                    ev.size(0) <= (1 << 24),
-                "ft_sgemm: fault-log events must be (capacity, ",
-                (int)ftsgemm::FLOG_EVENT_DWORDS, ") int32");
-    flog.counters = cn.mutable_data_ptr<int>();
-    flog.events = ev.mutable_data_ptr<int>();
-    flog.capacity = (int)ev.size(0);
-  }
-  TORCH_CHECK(ftsgemm::sgemm_tier_supported((int)tier, M, N, K),
-              "ft_sgemm: tier ", tier, " requires M,N,K multiples of its "
-              "tile (M=", M, " N=", N, " K=", K, ")");
-  auto stream = at::cuda::getCurrentCUDAStream();
-  ftsgemm::GemmArgs g{abft, inject, (int)M, (int)N, (int)K,
-                      a.const_data_ptr<float>(), b.const_data_ptr<float>(),
-                      c.mutable_data_ptr<float>(), (float)alpha, (float)beta,
-                      (float)tau, (float)inj_mag, (int)verify_windows};
-  g.stream = stream.stream();
-  g.log = flog.counters ? &flog : nullptr;
-  at::Tensor ws;
-  if (abft) {
-    // segment-checksum scratch (SA), via the caching allocator
-    size_t n = ftsgemm::sgemm_abft_workspace_floats((int)tier, (int)M,
-                                                    (int)N, (int)K);
-    ws = at::empty({(int64_t)n}, a.options());
-    g.ws = ws.mutable_data_ptr<float>();
-  }
-  hipError_t err = ftsgemm::sgemm_tier_launch((int)tier, g);
-  TORCH_CHECK(err == hipSuccess,
-              "ft_sgemm launch failed: ", hipGetErrorString(err));
+  ftsgemm::GemmArgs g{};
+  g.M = (int)M, g.N = (int)N, g.K = (int)K;
+  launch_gemm("ft_sgemm", tier, g, abft, inject, a, b, c, alpha, beta, tau,
+              inj_mag, verify_windows, counters, events, /*log_batch=*/0);
 }
 
-// Layout of a strided-batched call (mirrors ops.batched_layout, the Python
-// helper that raises ValueError before a call gets here): a (B,K,M),
-// b (B,K,N), c (B,N,M), inner two dimensions contiguous, the batch stride
-// read from the tensor.
-struct BatchedLayout {
-  int64_t batch, M, N, K, sA, sB, sC;
-};
-
-BatchedLayout check_batched_inputs(const at::Tensor& a, const at::Tensor& b,
-                                   const at::Tensor& c) {
+// Layout of a strided-batched call, read off the tensors into the M, N, K,
+// batch and stride fields of a GemmArgs: a (B,K,M), b (B,K,N), c (B,N,M),
+// inner two dimensions contiguous, the batch stride whatever the tensor has.
+// What a launch asks of the batch size, the strides and the alignment is
+// gemm_args_error's to say (ops.batched_layout is the Python mirror that
+// raises ValueError before a call gets here).
+ftsgemm::GemmArgs check_batched_inputs(const at::Tensor& a,
+                                       const at::Tensor& b,
+                                       const at::Tensor& c) {
   const char* nm = "ft_sgemm_batched";
   TORCH_CHECK(a.is_cuda() && b.is_cuda() && c.is_cuda(), nm,
               ": tensors must be on a GPU device");
@@ -107,31 +145,26 @@ BatchedLayout check_batched_inputs(const at::Tensor& a, const at::Tensor& b,
               nm, ": fp32 only (SGEMM)");
   TORCH_CHECK(a.dim() == 3 && b.dim() == 3 && c.dim() == 3, nm,
               ": 3-D tensors a (B,K,M), b (B,K,N), c (B,N,M) expected");
-  BatchedLayout L{c.size(0), a.size(2), b.size(2), a.size(1),
-                  a.stride(0), b.stride(0), c.stride(0)};
-  TORCH_CHECK(L.batch >= 1 && L.batch <= 65535, nm, ": batch ", L.batch,
-              " outside 1..65535");
-  TORCH_CHECK(a.size(0) == L.batch && b.size(0) == L.batch, nm,
+  const int64_t batch = c.size(0), M = a.size(2), N = b.size(2),
+                K = a.size(1);
+  TORCH_CHECK(a.size(0) == batch && b.size(0) == batch, nm,
               ": a, b and c must have one batch size");
-  TORCH_CHECK(b.size(1) == L.K, nm, ": a is (B,K,M) and b must be (B,K,N)");
-  TORCH_CHECK(c.size(1) == L.N && c.size(2) == L.M, nm,
+  TORCH_CHECK(b.size(1) == K, nm, ": a is (B,K,M) and b must be (B,K,N)");
+  TORCH_CHECK(c.size(1) == N && c.size(2) == M, nm,
               ": c must be (B,N,M) for column-major MxN");
-  TORCH_CHECK(L.M >= 1 && L.N >= 1 && L.K >= 1, nm, ": empty matrix");
+  TORCH_CHECK(batch >= 1 && M >= 1 && N >= 1 && K >= 1, nm,
+              ": empty batch or matrix");
+  TORCH_CHECK(batch <= INT32_MAX && M <= INT32_MAX && N <= INT32_MAX &&
+                  K <= INT32_MAX,
+              nm, ": a size beyond int32");
   for (const at::Tensor* t : {&a, &b, &c})
     TORCH_CHECK(t->stride(2) == 1 && t->stride(1) == t->size(2), nm,
                 ": the two inner dimensions must be contiguous");
-  if (L.batch == 1) L.sA = L.sB = 0, L.sC = L.M * L.N;  // strides unused
-  TORCH_CHECK(L.sA >= 0 && L.sB >= 0 && L.sA % 4 == 0 && L.sB % 4 == 0 &&
-                  L.sC % 4 == 0,
-              nm, ": batch strides must be multiples of 4 floats (", L.sA,
-              ", ", L.sB, ", ", L.sC, ")");
-  TORCH_CHECK(L.sC >= L.M * L.N, nm,
-              ": c entries must not overlap (batch stride ", L.sC, " < ",
-              L.M * L.N, ")");
-  for (const at::Tensor* t : {&a, &b, &c})
-    TORCH_CHECK(((uintptr_t)t->data_ptr() & 15) == 0, nm,
-                ": tensors must be 16-byte aligned");
-  return L;
+  ftsgemm::GemmArgs g{};
+  g.M = (int)M, g.N = (int)N, g.K = (int)K, g.batch = (int)batch;
+  if (batch > 1)  // a single entry takes the unbatched launch: no strides
+    g.strideA = a.stride(0), g.strideB = b.stride(0), g.strideC = c.stride(0);
+  return g;
 }
 
 // Floats of segment-checksum scratch a fused sgemm_batched call on these
@@ -139,81 +172,31 @@ BatchedLayout check_batched_inputs(const at::Tensor& a, const at::Tensor& b,
 // (batch stride 0), `batch` of them otherwise.
 int64_t batched_workspace_floats(int64_t tier, const at::Tensor& a,
                                  const at::Tensor& b, const at::Tensor& c) {
-  const BatchedLayout L = check_batched_inputs(a, b, c);
-  const int nA = L.sA == 0 ? 1 : (int)L.batch;
-  return (int64_t)ftsgemm::sgemm_abft_workspace_floats_batched(
-      (int)tier, (int)L.M, (int)L.N, (int)L.K, nA);
+  return (int64_t)ftsgemm::sgemm_abft_workspace_floats(
+      (int)tier, check_batched_inputs(a, b, c));
 }
 
 // Strided-batched twin of sgemm: one launch for the whole batch.  counters
-// (B, 5) / events (B, capacity, 8): one fault log per entry.
+// (B, 5) / events (B, capacity, 8): one fault log per entry
+// (attach_fault_log, batched form, for a batch of one as well).
 void sgemm_batched(int64_t tier, bool abft, bool inject, at::Tensor a,
                    at::Tensor b, at::Tensor c, double alpha, double beta,
                    double tau, double inj_mag, int64_t verify_windows,
                    c10::optional<at::Tensor> counters,
                    c10::optional<at::Tensor> events) {
-  const char* nm = "ft_sgemm_batched";
-  const BatchedLayout L = check_batched_inputs(a, b, c);
-  TORCH_CHECK(counters.has_value() == events.has_value(), nm,
-              ": fault-log counters and events go together");
-  ftsgemm::FaultLog flog;
-  if (counters.has_value()) {
-    const at::Tensor& cn = *counters;
-    const at::Tensor& ev = *events;
-    TORCH_CHECK(abft, nm, ": a fault log needs a fused-ABFT kernel");
-    TORCH_CHECK(cn.scalar_type() == at::kInt && ev.scalar_type() == at::kInt,
-                nm, ": fault-log tensors must be int32");
-    TORCH_CHECK(cn.is_contiguous() && ev.is_contiguous(), nm,
-                ": fault-log tensors must be contiguous");
-    TORCH_CHECK(cn.device() == a.device() && ev.device() == a.device(), nm,
-                ": fault-log tensors must be on the operands' device");
-    TORCH_CHECK(cn.dim() == 2 && cn.size(0) == L.batch &&
-                    cn.size(1) == ftsgemm::FLOG_N_COUNTERS,
-                nm, ": fault-log counters must be (batch, ",
-                (int)ftsgemm::FLOG_N_COUNTERS, ") int32");
-    TORCH_CHECK(ev.dim() == 3 && ev.size(0) == L.batch &&
-                    ev.size(2) == ftsgemm::FLOG_EVENT_DWORDS &&
-                    ev.size(1) >= 1 && ev.size(1) <= (1 << 24),
-                nm, ": fault-log events must be (batch, capacity, ",
-                (int)ftsgemm::FLOG_EVENT_DWORDS, ") int32");
-    flog.counters = cn.mutable_data_ptr<int>();
-    flog.events = ev.mutable_data_ptr<int>();
-    flog.capacity = (int)ev.size(1);
-  }
-  TORCH_CHECK(ftsgemm::sgemm_tier_supported((int)tier, L.M, L.N, L.K), nm,
-              ": tier ", tier, " requires M,N,K multiples of its tile (M=",
-              L.M, " N=", L.N, " K=", L.K, ")");
-  auto stream = at::cuda::getCurrentCUDAStream();
-  ftsgemm::GemmArgs g{abft, inject, (int)L.M, (int)L.N, (int)L.K,
-                      a.const_data_ptr<float>(), b.const_data_ptr<float>(),
-                      c.mutable_data_ptr<float>(), (float)alpha, (float)beta,
-                      (float)tau, (float)inj_mag, (int)verify_windows};
-  g.stream = stream.stream();
-  g.log = flog.counters ? &flog : nullptr;
-  g.batch = (int)L.batch;
-  g.strideA = L.sA;
-  g.strideB = L.sB;
-  g.strideC = L.sC;
-  at::Tensor ws;
-  if (abft) {
-    ws = at::empty({batched_workspace_floats(tier, a, b, c)}, a.options());
-    g.ws = ws.mutable_data_ptr<float>();
-  }
-  hipError_t err = ftsgemm::sgemm_tier_launch((int)tier, g);
-  TORCH_CHECK(err == hipSuccess, nm,
-              " launch failed: ", hipGetErrorString(err));
+  launch_gemm("ft_sgemm_batched", tier, check_batched_inputs(a, b, c), abft,
+              inject, a, b, c, alpha, beta, tau, inj_mag, verify_windows,
+              counters, events, /*log_batch=*/c.size(0));
 }
 
-// Layout of a ragged call (mirrors ops.ragged_layout, the Python helper that
-// raises ValueError before a call gets here): a (K,M), b (K,N), c (N,M), any
-// sizes >= 1, unit inner stride, row stride >= row width.  The row stride is
-// the column-major leading dimension; a one-row tensor's is its width.
-struct RaggedLayout {
-  int64_t M, N, K, lda, ldb, ldc;
-};
-
-RaggedLayout check_ragged_inputs(const at::Tensor& a, const at::Tensor& b,
-                                 const at::Tensor& c) {
+// Layout of a ragged call, read off the tensors into the M, N, K, ragged and
+// leading-dimension fields of a GemmArgs: a (K,M), b (K,N), c (N,M), any
+// sizes >= 1, unit inner stride.  The row stride is the column-major leading
+// dimension; a one-row tensor's is its width.  That it must not be shorter
+// than the row is gemm_args_error's to say (ops.ragged_layout is the Python
+// mirror that raises ValueError before a call gets here).
+ftsgemm::GemmArgs check_ragged_inputs(const at::Tensor& a, const at::Tensor& b,
+                                      const at::Tensor& c) {
   const char* nm = "ft_sgemm_ragged";
   TORCH_CHECK(a.is_cuda() && b.is_cuda() && c.is_cuda(), nm,
               ": tensors must be on a GPU device");
@@ -225,88 +208,48 @@ RaggedLayout check_ragged_inputs(const at::Tensor& a, const at::Tensor& b,
               nm, ": fp32 only (SGEMM)");
   TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && c.dim() == 2, nm,
               ": 2-D tensors a (K,M), b (K,N), c (N,M) expected");
-  RaggedLayout L{a.size(1), b.size(1), a.size(0), 0, 0, 0};
-  TORCH_CHECK(L.M >= 1 && L.N >= 1 && L.K >= 1, nm, ": empty matrix");
-  TORCH_CHECK(b.size(0) == L.K, nm, ": a is (K,M) and b must be (K,N)");
-  TORCH_CHECK(c.size(0) == L.N && c.size(1) == L.M, nm,
+  const int64_t M = a.size(1), N = b.size(1), K = a.size(0);
+  TORCH_CHECK(M >= 1 && N >= 1 && K >= 1, nm, ": empty matrix");
+  TORCH_CHECK(b.size(0) == K, nm, ": a is (K,M) and b must be (K,N)");
+  TORCH_CHECK(c.size(0) == N && c.size(1) == M, nm,
               ": c must be (N,M) for column-major MxN");
+  TORCH_CHECK(M <= INT32_MAX && N <= INT32_MAX && K <= INT32_MAX - 64, nm,
+              ": a size beyond int32");
+  // 0 is GemmArgs' word for packed, so a broadcast row stride of 0 must not
+  // get through as a leading dimension
   const auto ld = [&](const at::Tensor& t, const char* which) {
     TORCH_CHECK(t.stride(1) == 1 || t.size(1) == 1, nm, ": ", which,
                 " must have a unit inner stride");
-    if (t.size(0) == 1) return t.size(1);
-    TORCH_CHECK(t.stride(0) >= t.size(1), nm, ": rows of ", which,
-                " overlap (row stride ", t.stride(0), " < ", t.size(1), ")");
-    TORCH_CHECK(t.stride(0) <= INT32_MAX, nm, ": row stride of ", which,
-                " too large");
-    return t.stride(0);
+    if (t.size(0) == 1) return (int)t.size(1);
+    TORCH_CHECK(t.stride(0) >= 1 && t.stride(0) <= INT32_MAX, nm,
+                ": row stride of ", which, " outside 1..2^31-1");
+    return (int)t.stride(0);
   };
-  L.lda = ld(a, "a");
-  L.ldb = ld(b, "b");
-  L.ldc = ld(c, "c");
-  return L;
+  ftsgemm::GemmArgs g{};
+  g.M = (int)M, g.N = (int)N, g.K = (int)K;
+  g.ragged = true;
+  g.lda = ld(a, "a"), g.ldb = ld(b, "b"), g.ldc = ld(c, "c");
+  return g;
 }
 
-// Ragged twin of sgemm: any M, N, K and row-strided operands.
+// Ragged twin of sgemm: any M, N, K and row-strided operands.  Fault log as
+// sgemm's.
 void sgemm_ragged(int64_t tier, bool abft, bool inject, at::Tensor a,
                   at::Tensor b, at::Tensor c, double alpha, double beta,
                   double tau, double inj_mag, int64_t verify_windows,
                   c10::optional<at::Tensor> counters,
                   c10::optional<at::Tensor> events) {
-  const char* nm = "ft_sgemm_ragged";
-  const RaggedLayout L = check_ragged_inputs(a, b, c);
-  TORCH_CHECK(counters.has_value() == events.has_value(), nm,
-              ": fault-log counters and events go together");
-  ftsgemm::FaultLog flog;
-  if (counters.has_value()) {
-    const at::Tensor& cn = *counters;
-    const at::Tensor& ev = *events;
-    TORCH_CHECK(abft, nm, ": a fault log needs a fused-ABFT kernel");
-    TORCH_CHECK(cn.scalar_type() == at::kInt && ev.scalar_type() == at::kInt,
-                nm, ": fault-log tensors must be int32");
-    TORCH_CHECK(cn.is_contiguous() && ev.is_contiguous(), nm,
-                ": fault-log tensors must be contiguous");
-    TORCH_CHECK(cn.device() == a.device() && ev.device() == a.device(), nm,
-                ": fault-log tensors must be on the operands' device");
-    TORCH_CHECK(cn.dim() == 1 && cn.size(0) >= ftsgemm::FLOG_N_COUNTERS, nm,
-                ": fault-log counters must hold ",
-                (int)ftsgemm::FLOG_N_COUNTERS, " int32");
-    TORCH_CHECK(ev.dim() == 2 && ev.size(1) == ftsgemm::FLOG_EVENT_DWORDS &&
-                    ev.size(0) <= (1 << 24),
-                nm, ": fault-log events must be (capacity, ",
-                (int)ftsgemm::FLOG_EVENT_DWORDS, ") int32");
-    flog.counters = cn.mutable_data_ptr<int>();
-    flog.events = ev.mutable_data_ptr<int>();
-    flog.capacity = (int)ev.size(0);
-  }
-  TORCH_CHECK(L.M <= INT32_MAX && L.N <= INT32_MAX && L.K <= INT32_MAX - 64,
-              nm, ": a size beyond int32");
-  auto stream = at::cuda::getCurrentCUDAStream();
-  ftsgemm::GemmArgs g{abft, inject, (int)L.M, (int)L.N, (int)L.K,
-                      a.const_data_ptr<float>(), b.const_data_ptr<float>(),
-                      c.mutable_data_ptr<float>(), (float)alpha, (float)beta,
-                      (float)tau, (float)inj_mag, (int)verify_windows};
-  g.stream = stream.stream();
-  g.log = flog.counters ? &flog : nullptr;
-  g.ragged = true;
-  g.lda = (int)L.lda;
-  g.ldb = (int)L.ldb;
-  g.ldc = (int)L.ldc;
-  at::Tensor ws;
-  if (abft) {
-    size_t n = ftsgemm::sgemm_abft_workspace_floats_ragged(
-        (int)tier, (int)L.M, (int)L.N, (int)L.K);
-    ws = at::empty({(int64_t)n}, a.options());
-    g.ws = ws.mutable_data_ptr<float>();
-  }
-  hipError_t err = ftsgemm::sgemm_tier_launch((int)tier, g);
-  TORCH_CHECK(err == hipSuccess, nm,
-              " launch failed: ", hipGetErrorString(err));
+  launch_gemm("ft_sgemm_ragged", tier, check_ragged_inputs(a, b, c), abft,
+              inject, a, b, c, alpha, beta, tau, inj_mag, verify_windows,
+              counters, events, /*log_batch=*/0);
 }
 
 int64_t ragged_workspace_floats(int64_t tier, int64_t M, int64_t N,
                                 int64_t K) {
-  return (int64_t)ftsgemm::sgemm_abft_workspace_floats_ragged(
-      (int)tier, (int)M, (int)N, (int)K);
+  ftsgemm::GemmArgs g{};
+  g.M = (int)M, g.N = (int)N, g.K = (int)K;
+  g.ragged = true;
+  return (int64_t)ftsgemm::sgemm_abft_workspace_floats((int)tier, g);
 }
 
 void rocblas_sgemm_nt(at::Tensor a, at::Tensor b, at::Tensor c, double alpha,

@@ -24,11 +24,12 @@ int main() {
   hipMemcpy(dB, h.data(), bytes, hipMemcpyHostToDevice);
 
   // fused-ABFT huge tier with the 20-fault self-test
-  size_t wsf = ftsgemm::sgemm_abft_workspace_floats(FT_TIER_ID_huge, n, n, n);
-  hipMalloc(&ws, wsf * sizeof(float));
   ftsgemm::GemmArgs g{/*abft=*/true, /*inject=*/true, n, n, n, dA, dB, dC,
                       /*alpha=*/1.f, /*beta=*/0.f, /*tau=*/9500.f,
-                      /*inj_mag=*/10000.f, /*verify_windows=*/20, ws};
+                      /*inj_mag=*/10000.f, /*verify_windows=*/20};
+  size_t wsf = ftsgemm::sgemm_abft_workspace_floats(FT_TIER_ID_huge, g);
+  hipMalloc(&ws, wsf * sizeof(float));
+  g.ws = ws;
   hipError_t err = ftsgemm::sgemm_tier_launch(FT_TIER_ID_huge, g);
   if (err != hipSuccess) {
     fprintf(stderr, "launch failed: %s\n", hipGetErrorString(err));
@@ -46,8 +47,7 @@ int main() {
   gb.batch = 4;
   gb.strideA = 0;
   gb.strideB = gb.strideC = (long long)nb * nb;
-  if (ftsgemm::sgemm_abft_workspace_floats_batched(FT_TIER_ID_huge, nb, nb,
-                                                   nb, /*nA=*/1) > wsf)
+  if (ftsgemm::sgemm_abft_workspace_floats(FT_TIER_ID_huge, gb) > wsf)
     return 1;
   err = ftsgemm::sgemm_tier_launch(FT_TIER_ID_huge, gb);
   if (err != hipSuccess) {
@@ -63,8 +63,7 @@ int main() {
                        dB + 1, dC + 1, 1.f, 0.f, 9500.f, 10000.f, 20, ws};
   gr.ragged = true;
   gr.lda = gr.ldb = gr.ldc = n;
-  if (ftsgemm::sgemm_abft_workspace_floats_ragged(FT_TIER_ID_large, 1001, 999,
-                                                  333) > wsf)
+  if (ftsgemm::sgemm_abft_workspace_floats(FT_TIER_ID_large, gr) > wsf)
     return 1;
   err = ftsgemm::sgemm_tier_launch(FT_TIER_ID_large, gr);
   if (err != hipSuccess) {

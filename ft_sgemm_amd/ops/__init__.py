@@ -44,13 +44,27 @@ def tier_index(tier: str) -> int:
     return TIERS.index(tier)
 
 
+def _launch(entry: str, tier: str, a, b, c, alpha, beta, fused=None,
+            report=None):
+    """The one call into the binding `entry` (sgemm, sgemm_batched or
+    sgemm_ragged): plain when fused is None, otherwise the fused-ABFT twin
+    with fused = (inject, tau, inj_mag, verify_windows) and the optional
+    fault report."""
+    abft = fused is not None
+    inject, tau, inj_mag, verify_windows = fused if abft else (False, 0.0,
+                                                               0.0, 20)
+    log = (None, None) if report is None else (report.counters, report.events)
+    getattr(_require_ext(), entry)(tier_index(tier), abft, inject, a, b, c,
+                                   alpha, beta, tau, inj_mag, verify_windows,
+                                   *log)
+    return c
+
+
 def sgemm(tier: str, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
           alpha: float = 1.0, beta: float = 0.0) -> torch.Tensor:
     """Plain hand-tiled MFMA SGEMM.  a:(K,M) b:(K,N) c:(N,M) fp32 CUDA
     tensors holding column-major A (MxK), B (NxK), C (MxN).  In-place on c."""
-    _require_ext().sgemm(tier_index(tier), False, False, a, b, c,
-                         alpha, beta, 0.0, 0.0, 20)
-    return c
+    return _launch("sgemm", tier, a, b, c, alpha, beta)
 
 
 def ft_sgemm(tier: str, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
@@ -68,14 +82,8 @@ def ft_sgemm(tier: str, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
     accumulates across launches until report.reset().  The launch does not
     synchronise; report.read() does.  C is bit-identical with and without
     a report."""
-    if report is None:
-        _require_ext().sgemm(tier_index(tier), True, inject, a, b, c,
-                             alpha, beta, tau, inj_mag, verify_windows)
-    else:
-        _require_ext().sgemm(tier_index(tier), True, inject, a, b, c,
-                             alpha, beta, tau, inj_mag, verify_windows,
-                             report.counters, report.events)
-    return c
+    return _launch("sgemm", tier, a, b, c, alpha, beta,
+                   (inject, tau, inj_mag, verify_windows), report)
 
 
 MAX_BATCH = 65535  # the batch index rides in gridDim.z
@@ -84,7 +92,8 @@ MAX_BATCH = 65535  # the batch index rides in gridDim.z
 def batched_layout(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor):
     """Validate the operands of a strided-batched call and return
     (batch, m, n, k, sA, sB, sC), the batch strides in floats.  Runs on any
-    device; the C++ binding repeats the same checks.
+    device: the CPU-runnable mirror of the launch rules, which the C++ side
+    states once, in gemm_args_error (csrc/dispatch.hip).
 
     a is (B, K, M) or (K, M), b is (B, K, N) or (K, N), c is (B, N, M).  A
     2-D operand is shared by every entry (stride 0), exactly like an
@@ -150,9 +159,7 @@ def sgemm_batched(tier: str, a: torch.Tensor, b: torch.Tensor,
     sgemm on that entry with the classic (non-stream-K) decomposition;
     FT_SGEMM_STREAMK has no effect on a batch of more than one."""
     a3, b3 = _batched_operands(a, b, c)
-    _require_ext().sgemm_batched(tier_index(tier), False, False, a3, b3, c,
-                                 alpha, beta, 0.0, 0.0, 20)
-    return c
+    return _launch("sgemm_batched", tier, a3, b3, c, alpha, beta)
 
 
 def ft_sgemm_batched(tier: str, a: torch.Tensor, b: torch.Tensor,
@@ -167,25 +174,18 @@ def ft_sgemm_batched(tier: str, a: torch.Tensor, b: torch.Tensor,
     injector rotates per entry, as in ft_sgemm.  report: a
     BatchedFaultReport of the same batch size; entry i logs into slot i."""
     a3, b3 = _batched_operands(a, b, c)
-    if report is None:
-        _require_ext().sgemm_batched(tier_index(tier), True, inject, a3, b3,
-                                     c, alpha, beta, tau, inj_mag,
-                                     verify_windows)
-    else:
-        if report.batch != c.shape[0]:
-            raise ValueError(f"ft_sgemm_batched: report holds {report.batch} "
-                             f"entries, the batch {c.shape[0]}")
-        _require_ext().sgemm_batched(tier_index(tier), True, inject, a3, b3,
-                                     c, alpha, beta, tau, inj_mag,
-                                     verify_windows, report.counters,
-                                     report.events)
-    return c
+    if report is not None and report.batch != c.shape[0]:
+        raise ValueError(f"ft_sgemm_batched: report holds {report.batch} "
+                         f"entries, the batch {c.shape[0]}")
+    return _launch("sgemm_batched", tier, a3, b3, c, alpha, beta,
+                   (inject, tau, inj_mag, verify_windows), report)
 
 
 def ragged_layout(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor):
     """Validate the operands of a ragged call and return
     (m, n, k, lda, ldb, ldc), the leading dimensions in floats.  Runs on any
-    device; the C++ binding repeats the same checks.
+    device: the CPU-runnable mirror of the launch rules, which the C++ side
+    states once, in gemm_args_error (csrc/dispatch.hip).
 
     a is (K, M), b is (K, N), c is (N, M), fp32, any sizes >= 1.  The inner
     stride must be 1 and the row stride at least the row width, so packed
@@ -233,9 +233,7 @@ def sgemm_ragged(tier: str, a: torch.Tensor, b: torch.Tensor,
     the bits of sgemm with the classic (non-stream-K) decomposition.
     In-place on c."""
     ragged_layout(a, b, c)
-    _require_ext().sgemm_ragged(tier_index(tier), False, False, a, b, c,
-                                alpha, beta, 0.0, 0.0, 20)
-    return c
+    return _launch("sgemm_ragged", tier, a, b, c, alpha, beta)
 
 
 def ft_sgemm_ragged(tier: str, a: torch.Tensor, b: torch.Tensor,
@@ -250,14 +248,8 @@ def ft_sgemm_ragged(tier: str, a: torch.Tensor, b: torch.Tensor,
     a victim may lie in the padding: it is corrected like any other and
     reported with its padded coordinates (FaultReport)."""
     ragged_layout(a, b, c)
-    if report is None:
-        _require_ext().sgemm_ragged(tier_index(tier), True, inject, a, b, c,
-                                    alpha, beta, tau, inj_mag, verify_windows)
-    else:
-        _require_ext().sgemm_ragged(tier_index(tier), True, inject, a, b, c,
-                                    alpha, beta, tau, inj_mag, verify_windows,
-                                    report.counters, report.events)
-    return c
+    return _launch("sgemm_ragged", tier, a, b, c, alpha, beta,
+                   (inject, tau, inj_mag, verify_windows), report)
 
 
 def rocblas_sgemm(a, b, c, alpha: float = 1.0, beta: float = 0.0):

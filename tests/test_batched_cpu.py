@@ -218,7 +218,7 @@ def test_every_tier_has_a_batched_tu_matching_the_table():
     for name, t in TILING.items():
         src = open(os.path.join(gen, f"kernel_{name}_batched.hip")).read()
         m = re.search(r"hipError_t launch_tier_batched_(\w+)\(const GemmArgs& "
-                      r"g\) \{\s*return launch_tier_batched<([^>]*)>\(g\);",
+                      r"g\) \{\s*return launch_tier<([^>]*), true>\(g\);",
                       src)
         assert m, name
         mm = 16 if t["mfma"] == "f32_16x16x4" else 32

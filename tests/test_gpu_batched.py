@@ -13,6 +13,8 @@ at these tile counts and sum in another order.  Against them the batched
 result must be BIT-identical: same kernel body, same tiles, same order.
 """
 
+import math
+
 import pytest
 import torch
 
@@ -223,25 +225,169 @@ def test_batch_of_one_is_the_single_launch(tier):
         assert torch.equal(c_b[0], c_s), mode
 
 
-def test_binding_rejects_bad_launches():
-    tier = "medium"
+# ---- the launch rules, through the raw bindings ---------------------------
+# One statement of the rules (gemm_args_error, csrc/dispatch.hip) and one
+# fault-log check behind all three entries: every rule that can be broken
+# from tensors is broken once through every entry it applies to.  Medium tier
+# at one tile; nothing is launched.
+
+REJ_TIER = "medium"
+ENTRIES = ("sgemm", "sgemm_batched", "sgemm_ragged")
+TILED = ("sgemm", "sgemm_batched")
+
+
+def _rej_operands(entry, m=None, n=None, k=None):
+    """A launchable call of `entry`: one tile, a batch of BATCH for the
+    batched entry.  c is a view of c_flat."""
+    t = TILING[REJ_TIER]
+    m, n, k = m or t["bm"], n or t["bn"], k or t["bk"]
+    lead = (BATCH,) if entry == "sgemm_batched" else ()
+    g = torch.Generator(device="cpu").manual_seed(99)
+
+    def rand(*shape):
+        return torch.rand(shape, generator=g).cuda()
+
+    c_flat = rand(BATCH * n * m)
+    return dict(a=rand(*lead, k, m), b=rand(*lead, k, n), c_flat=c_flat,
+                c=c_flat[:math.prod(lead) * n * m].view(*lead, n, m),
+                abft=False, log=(None, None))
+
+
+def _log(entry, device="cuda"):
+    lead = (BATCH,) if entry == "sgemm_batched" else ()
+    return (torch.full(lead + (5,), 7, dtype=torch.int32, device=device),
+            torch.full(lead + (4, 8), 7, dtype=torch.int32, device=device))
+
+
+def _misfit(dim):
+    def build(entry):
+        t = TILING[REJ_TIER]
+        size = dict(m=t["bm"], n=t["bn"], k=t["bk"])
+        size[dim] //= 2  # 16, 16 or 8: still multiples of 4
+        return _rej_operands(entry, **size)
+    return build
+
+
+def _stride_not_4(entry):
+    d = _rej_operands(entry)
+    _, k, m = d["a"].shape
+    step = k * m + 2
+    d["a"] = torch.zeros(BATCH * step, device="cuda").as_strided(
+        (BATCH, k, m), (step, m, 1))
+    return d
+
+
+def _c_entries_overlap(entry):
+    d = _rej_operands(entry)
+    _, n, m = d["c"].shape
+    d["c"] = d["c_flat"].as_strided((BATCH, n, m), (n * m - 4, m, 1))
+    return d
+
+
+def _offset_base(entry):
+    d = _rej_operands(entry)
+    shape = d["a"].shape
+    d["a"] = torch.zeros(d["a"].numel() + 1, device="cuda")[1:].view(shape)
+    assert d["a"].data_ptr() % 16 == 4
+    return d
+
+
+def _short_row_stride(which):
+    def build(entry):
+        d = _rej_operands(entry)
+        rows, width = d[which].shape
+        d[which] = d["c_flat"].as_strided((rows, width), (width - 1, 1))
+        return d
+    return build
+
+
+def _bad_log(how):
+    def build(entry):
+        d = _rej_operands(entry)
+        d["abft"] = how != "plain"
+        cn, ev = _log(entry)
+        if how == "rank":
+            cn = cn.reshape(-1) if cn.dim() == 2 else cn.reshape(1, -1)
+        elif how == "dtype":
+            cn = cn.long()
+        elif how == "device":
+            ev = ev.cpu()
+        elif how == "alone":
+            ev = None
+        d["log"] = (cn, ev)
+        return d
+    return build
+
+
+def _tile_text(dim):
+    t = TILING[REJ_TIER]
+    size = dict(m=t["bm"], n=t["bn"], k=t["bk"])
+    size[dim] //= 2
+    return (r"multiples of its tile.*M={m} N={n} K={k}\b".format(**size))
+
+
+# name: (entries, text of the error, builder)
+REJECTIONS = {
+    "misfit_m": (TILED, _tile_text("m"), _misfit("m")),
+    "misfit_n": (TILED, _tile_text("n"), _misfit("n")),
+    "misfit_k": (TILED, _tile_text("k"), _misfit("k")),
+    "stride_not_4": (("sgemm_batched",), "multiples of 4", _stride_not_4),
+    "c_entries_overlap": (("sgemm_batched",), "overlap", _c_entries_overlap),
+    "offset_base": (("sgemm_batched",), "16-byte aligned", _offset_base),
+    "short_row_a": (("sgemm_ragged",), "shorter than", _short_row_stride("a")),
+    "short_row_b": (("sgemm_ragged",), "shorter than", _short_row_stride("b")),
+    "short_row_c": (("sgemm_ragged",), "shorter than", _short_row_stride("c")),
+    "log_rank": (ENTRIES, "fault-log counters must", _bad_log("rank")),
+    "log_dtype": (ENTRIES, "must be int32", _bad_log("dtype")),
+    "log_device": (ENTRIES, "operands' device", _bad_log("device")),
+    "log_alone": (ENTRIES, "go together", _bad_log("alone")),
+    "log_on_plain": (ENTRIES, "needs a fused-ABFT kernel", _bad_log("plain")),
+}
+
+
+@pytest.mark.parametrize("entry,case", [
+    pytest.param(e, name, id=f"{name}-{e}")
+    for name, (entries, _, _) in REJECTIONS.items() for e in entries])
+def test_binding_rejects_bad_launches(entry, case):
+    _, text, build = REJECTIONS[case]
+    d = build(entry)
+    watched = [d["c_flat"]] + [x for x in d["log"] if x is not None]
+    before = [x.clone() for x in watched]
+    with pytest.raises(RuntimeError, match=text):
+        getattr(ops._require_ext(), entry)(
+            ops.tier_index(REJ_TIER), d["abft"], False, d["a"], d["b"],
+            d["c"], 1.0, 0.0, 0.0, 0.0, 20, *d["log"])
+    torch.cuda.synchronize()
+    for x, x0 in zip(watched, before):
+        assert torch.equal(x, x0), "a rejected call wrote to its tensors"
+
+
+@pytest.mark.parametrize("tier", TIERS)
+def test_workspace_query_is_the_formula(tier):
+    """2 * ceil(M / wm) * round_up(K, 64) floats, times the batch when every
+    entry has an A of its own: the one C++ query behind both bindings."""
+    t = TILING[tier]
+    bm, bn, bk = t["bm"], t["bn"], t["bk"]
     ext = ops._require_ext()
     ti = ops.tier_index(tier)
-    a, b, c0 = operands(tier)
-    m, n, k = shape(tier)
-    args = (1.0, 0.0, 0.0, 0.0, 20)
-    # batch stride of a not a multiple of 4 floats
-    step = k * m + 2
-    a_bad = torch.zeros(BATCH * step, device="cuda").as_strided(
-        (BATCH, k, m), (step, m, 1))
-    c = c0.clone()
-    with pytest.raises(RuntimeError, match="multiples of 4"):
-        ext.sgemm_batched(ti, False, False, a_bad, b, c, *args)
-    # M not a multiple of the tile
-    a16 = a[:, :, :16].contiguous()
-    c16 = c0[:, :, :16].contiguous()
-    c16_0 = c16.clone()
-    with pytest.raises(RuntimeError, match="multiples of its tile"):
-        ext.sgemm_batched(ti, False, False, a16, b, c16, *args)
-    torch.cuda.synchronize()
-    assert torch.equal(c, c0) and torch.equal(c16, c16_0)
+
+    def want(m, k, n_a=1):
+        return 2 * -(-m // t["wm"]) * (-(-k // 64) * 64) * n_a
+
+    def batched(batch, shared_a):
+        a = torch.empty((1 if shared_a else batch, bk, bm), device="cuda")
+        return ext.batched_workspace_floats(
+            ti, a.expand(batch, bk, bm),
+            torch.empty((batch, bk, bn), device="cuda"),
+            torch.empty((batch, bn, bm), device="cuda"))
+
+    # one tile, as a batch of one and as a ragged call
+    assert batched(1, False) == want(bm, bk)
+    assert ext.ragged_workspace_floats(ti, bm, bn, bk) == want(bm, bk)
+    # one row past a band, K past a multiple of 64
+    assert ext.ragged_workspace_floats(ti, bm + 1, bn + 1, 65) == \
+        want(bm + 1, 65)
+    assert want(bm + 1, 65) == 2 * (bm // t["wm"] + 1) * 128
+    # a batch of 3, A shared (stride 0) and not
+    assert batched(3, True) == want(bm, bk)
+    assert batched(3, False) == want(bm, bk, 3)
