@@ -16,7 +16,10 @@ namespace ftsgemm {
 #define FT_DECL(name, BM, BN, BK, WM, WN, MM)              \
   hipError_t launch_tier_##name(const GemmArgs& g);         \
   hipError_t launch_tier_batched_##name(const GemmArgs& g); \
-  hipError_t launch_tier_ragged_##name(const GemmArgs& g);
+  hipError_t launch_tier_ragged_##name(const GemmArgs& g);    \
+  hipError_t launch_tier_ragged_tn_##name(const GemmArgs& g); \
+  hipError_t launch_tier_ragged_nt_##name(const GemmArgs& g); \
+  hipError_t launch_tier_ragged_tt_##name(const GemmArgs& g);
 FT_TIER_LIST(FT_DECL)
 #undef FT_DECL
 
@@ -27,12 +30,16 @@ namespace {
 struct TierRow {
   hipError_t (*launch)(const GemmArgs&);
   hipError_t (*launch_batched)(const GemmArgs&);  // batch > 1
-  hipError_t (*launch_ragged)(const GemmArgs&);   // g.ragged
+  // g.ragged, indexed by transA + 2 * transB: one translation unit each
+  hipError_t (*launch_ragged[4])(const GemmArgs&);
   int bm, bn, bk, wm;
 };
 const TierRow kTiers[FT_N_TIERS] = {
-#define FT_ROW(name, BM, BN, BK, WM, WN, MM)                             \
-  {launch_tier_##name, launch_tier_batched_##name, launch_tier_ragged_##name, \
+#define FT_ROW(name, BM, BN, BK, WM, WN, MM)                        \
+  {launch_tier_##name,                                              \
+   launch_tier_batched_##name,                                      \
+   {launch_tier_ragged_##name, launch_tier_ragged_tn_##name,        \
+    launch_tier_ragged_nt_##name, launch_tier_ragged_tt_##name},    \
    BM, BN, BK, WM},
     FT_TIER_LIST(FT_ROW)
 #undef FT_ROW
@@ -64,11 +71,14 @@ const char* gemm_args_error(int tier, const GemmArgs& g) {
   if (g.abft && !g.ws) return "a fused-ABFT launch needs its workspace ws";
   const uintptr_t ptrs =
       (uintptr_t)g.A | (uintptr_t)g.B | (uintptr_t)g.C | (uintptr_t)g.ws;
+  if ((g.transA || g.transB) && !g.ragged)
+    return "transA / transB need a ragged launch";
   if (g.ragged) {
     if (g.batch != 1) return "a ragged launch is one product (batch == 1)";
-    // a leading dimension may pad its rows, never cut them
-    if ((g.lda && g.lda < g.M) || (g.ldb && g.ldb < g.N) ||
-        (g.ldc && g.ldc < g.M))
+    // a leading dimension may pad its rows, never cut them; a transposed
+    // operand's rows run along k
+    if ((g.lda && g.lda < (g.transA ? g.K : g.M)) ||
+        (g.ldb && g.ldb < (g.transB ? g.K : g.N)) || (g.ldc && g.ldc < g.M))
       return "a leading dimension is shorter than its rows";
     if (ptrs & 3) return "A, B, C and ws must be 4-byte aligned";
     if ((g.N + t->bn - 1) / t->bn > kMaxGridYZ)
@@ -94,7 +104,8 @@ const char* gemm_args_error(int tier, const GemmArgs& g) {
 hipError_t sgemm_tier_launch(int tier, const GemmArgs& g) {
   if (gemm_args_error(tier, g)) return hipErrorInvalidValue;
   const TierRow& t = kTiers[tier];
-  if (g.ragged) return t.launch_ragged(g);
+  if (g.ragged)
+    return t.launch_ragged[(g.transA ? 1 : 0) + (g.transB ? 2 : 0)](g);
   return g.batch > 1 ? t.launch_batched(g) : t.launch(g);
 }
 

@@ -39,6 +39,12 @@ namespace ftsgemm {
 // ceil tile counts.  A fault injected into an edge tile's padding is logged
 // with its padded coordinates (fault_log.h).
 //
+// transA / transB (ragged launches only) take that operand transposed, i.e.
+// row-major: with transA, element (i, k) of the logical M x K matrix A is at
+// A[k + i*lda] with lda >= K (0 = packed = K); transB likewise for B with
+// ldb >= K.  C, the workspace and its size are unchanged, and the result has
+// the bits of the untransposed launch on the transposed copy.
+//
 // Which shapes, strides, leading dimensions and alignments each of the three
 // forms accepts is stated once, in gemm_args_error.
 struct GemmArgs {
@@ -55,6 +61,7 @@ struct GemmArgs {
   long long strideA = 0, strideB = 0, strideC = 0;
   bool ragged = false;
   int lda = 0, ldb = 0, ldc = 0;  // ragged only; 0 = packed
+  bool transA = false, transB = false;  // ragged only
 };
 
 // The launch rules: nullptr when sgemm_tier_launch(tier, g) may launch g,

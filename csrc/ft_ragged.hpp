@@ -21,6 +21,16 @@
 // detected, located, corrected and logged like any other, with its true
 // padded coordinates (fault_log.h).
 //
+// Transposed operands (template flags TA / TB, GemmArgs::transA / transB): a
+// row-major operand, element (row, k) at g[k + row*ld], is a third way to fill
+// the same [k][row] LDS panel.  stage_operand_guarded_t is the always-legal
+// 4-B form; stage_operand_t is the fast one (16 B per lane along k into
+// registers, transposed into LDS with 4-B writes after the panel's MFMA
+// loop).  Everything after the staging is shared, so a transposed call has
+// the bits of the plain call on the transposed copy.  The TA = TB = false
+// instantiations are the kernels as they were and keep their own translation
+// units; the others live in kernel_<tier>_ragged_{tn,nt,tt}.hip.
+//
 // Classic decomposition only: no stream-K, no batch.
 
 #pragma once
@@ -62,6 +72,102 @@ __device__ __attribute__((always_inline)) inline void stage_operand_guarded(
   }
 }
 
+// stage_operand_guarded for a transposed (row-major) operand: element
+// (row i, k) is at g[k + i*ld].  The same lane -> (k, row) map and the same
+// LDS image; consecutive lanes are ld floats apart in memory, so it is slow.
+// It serves unaligned operands, edge blocks and the K tail.
+template <int ROWS, int BK, int THREADS>
+__device__ __attribute__((always_inline)) inline void stage_operand_guarded_t(
+    float* dst, const float* __restrict__ g, int ld, int rows, int K, int row0,
+    int k0, int tid, int wave) {
+  static_assert((ROWS * BK) % THREADS == 0, "whole 4-B passes");
+  constexpr int NP = (ROWS * BK) / THREADS;
+#pragma unroll
+  for (int t = 0; t < NP; ++t) {
+    const int f = t * THREADS + tid;
+    const int k = k0 + f / ROWS, i = row0 + f % ROWS;
+    const float* src =
+        (i < rows && k < K) ? g + k + (size_t)i * ld : ragged_zero_word;
+    glds<4>(src, dst + t * THREADS + wave * 64);
+  }
+}
+
+// Which lane of a pass loads which 16-B quad (row, kq) of a transposed panel.
+// FT_TRANS_ROW_FASTEST unset (shipped): the BK/4 quads of a row sit in
+// consecutive lanes, so a wave reads whole 4*BK-byte row segments; the four
+// 4-B LDS writes of a lane then go to bank row % 32 and are (BK/4)-way
+// conflicted when ROWS is a multiple of 32.  Set: row fastest, conflict-free
+// LDS writes, but the quads of one row segment are ROWS lanes apart.
+// docs/ABLATION.md section 16 has both measured.
+#ifdef FT_TRANS_ROW_FASTEST
+constexpr bool kTransRowFastest = true;
+#else
+constexpr bool kTransRowFastest = false;
+#endif
+
+// Fast staging of a transposed operand, legal when the operand is 16-B
+// aligned with ld % 4 == 0, the block's ROWS rows all exist and the panel is a
+// whole one: load() reads 16 B per lane along k into registers
+// (global_load_dwordx4), store() writes their transpose into the [k][row]
+// panel with 4-B LDS writes — the image stage_operand leaves for the same
+// values.  global_load_lds cannot do this (its LDS side is lane-linear).
+// Passes may be fractional in whole waves, as in stage_operand.
+template <int ROWS, int BK, int THREADS>
+struct stage_operand_t {
+  static constexpr int QPR = BK / 4;        // 16-B quads per row
+  static constexpr int NQ = ROWS * QPR;     // quads per panel
+  static constexpr int GF = NQ / THREADS;   // full passes
+  static constexpr int GR = NQ % THREADS;   // remainder lanes
+  static constexpr int NP = GF + (GR > 0 ? 1 : 0);
+  static_assert(BK % 4 == 0, "16-B reads along k");
+  static_assert(GR % 64 == 0, "stage remainder must be whole waves");
+  static_assert(NP > 0, "tile too small");
+  using regs = f32x4[NP];
+
+  static __device__ __attribute__((always_inline)) inline void quad(
+      int c, int& row, int& kq) {
+    if constexpr (kTransRowFastest) {
+      row = c % ROWS, kq = c / ROWS;
+    } else {
+      kq = c % QPR, row = c / QPR;
+    }
+  }
+  static __device__ __attribute__((always_inline)) inline void load(
+      regs& v, const float* __restrict__ g, int ld, int row0, int k0,
+      int tid) {
+#pragma unroll
+    for (int t = 0; t < NP; ++t) {
+      if (t < GF || tid < GR) {
+        int row, kq;
+        quad(t * THREADS + tid, row, kq);
+        v[t] = *(const f32x4*)(g + (k0 + 4 * kq) + (size_t)(row0 + row) * ld);
+      }
+    }
+  }
+  static __device__ __attribute__((always_inline)) inline void store(
+      const regs& v, float* dst, int tid) {
+#pragma unroll
+    for (int t = 0; t < NP; ++t) {
+      if (t < GF || tid < GR) {
+        int row, kq;
+        quad(t * THREADS + tid, row, kq);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) dst[(4 * kq + u) * ROWS + row] = v[t][u];
+      }
+    }
+  }
+};
+
+// The sums of four consecutive rows that both segment-sum kernels combine:
+// plain (v0+v1)+(v2+v3) and row-weighted with i0 = the first row's index in
+// its band.  One function, so that contraction into fmas is decided once and
+// the two kernels give the same bits.
+__device__ __attribute__((always_inline)) inline void segsum_rows4(
+    const f32x4& v, float i0, float& s, float& w) {
+  s = (v[0] + v[1]) + (v[2] + v[3]);
+  w = i0 * v[0] + (i0 + 1.f) * v[1] + (i0 + 2.f) * v[2] + (i0 + 3.f) * v[3];
+}
+
 // Ragged segment sums: segsum_column for any M and leading dimension, plus
 // the zero fill the ragged kernel's last panel relies on.  Launched on sstr
 // blocks.  Block k < K writes, per SEG-row band (ceil(M/SEG) of them), the
@@ -99,10 +205,8 @@ __global__ __launch_bounds__(256) void segsum_ragged_kernel(
       for (int u = 0; u < 4; ++u)
         if (idx + u < M) v[u] = col[idx + u];
     }
-    float s = (v[0] + v[1]) + (v[2] + v[3]);
-    const float i0 = (float)(idx % SEG);
-    float w = i0 * v[0] + (i0 + 1.f) * v[1] + (i0 + 2.f) * v[2] +
-              (i0 + 3.f) * v[3];
+    float s, w;
+    segsum_rows4(v, (float)(idx % SEG), s, w);
 #pragma unroll
     for (int m = 1; m < GL; m <<= 1) {
       s += __shfl_xor(s, m, 64);
@@ -115,14 +219,65 @@ __global__ __launch_bounds__(256) void segsum_ragged_kernel(
   }
 }
 
+// Plain and weighted sums of rows [4*g0, 4*(g0+NG)) of one band at one k of a
+// transposed A: the 4-row sums of segsum_rows4 combined by the balanced
+// pairwise tree that segsum_ragged_kernel's xor butterfly forms (lane 0 of a
+// group adds, level by level, the sum of the next 1, 2, 4, ... lanes).
+template <int NG>
+__device__ __attribute__((always_inline)) inline void segsum_t_tree(
+    const float* __restrict__ p, size_t lda, int row0, int g0, int M, float& s,
+    float& w) {
+  if constexpr (NG == 1) {
+    f32x4 v{0.f, 0.f, 0.f, 0.f};
+    const int i = row0 + 4 * g0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (i + u < M) v[u] = p[(size_t)(i + u) * lda];
+    segsum_rows4(v, (float)(4 * g0), s, w);
+  } else {
+    float s1, w1;
+    segsum_t_tree<NG / 2>(p, lda, row0, g0, M, s, w);
+    segsum_t_tree<NG / 2>(p, lda, row0, g0 + NG / 2, M, s1, w1);
+    s += s1;
+    w += w1;
+  }
+}
+
+// segsum_ragged_kernel for a transposed A (element (i, k) at A[k + i*lda]):
+// the same workspace, the same zero fill of [K, sstr) and the same bits.
+// Threads run along k, so the reads are coalesced; blockIdx.x is the band and
+// each thread walks its band's SEG rows.  Rows >= M contribute exact zeros.
+template <int SEG>
+__global__ __launch_bounds__(256) void segsum_ragged_t_kernel(
+    int M, int K, int lda, int sstr, const float* __restrict__ A,
+    float* __restrict__ S) {
+  const int band = blockIdx.x;
+  float* out = S + (size_t)band * 2 * sstr;
+  for (int k = blockIdx.y * 256 + threadIdx.x; k < sstr;
+       k += gridDim.y * 256) {
+    float s = 0.f, w = 0.f;
+    if (k < K) segsum_t_tree<SEG / 4>(A + k, (size_t)lda, band * SEG, 0, M, s, w);
+    out[2 * k] = s;  // ws is only 4-B aligned: no 8-B store
+    out[2 * k + 1] = w;
+  }
+}
+
 // The ragged kernel.  Work decomposition, panel body, injector, verify and
 // the per-element epilogue expression are sgemm_mfma's; what differs is the
 // staging (fast 16-B path on a block and panel where it is legal, guarded
 // 4-B path elsewhere — both give the same LDS contents, so C does not depend
 // on which ran), the strip of a wave whose whole band lies below row M
 // (zeros), and the guarded epilogue.
+//
+// TA / TB: that operand is transposed (lda / ldb then run along k).  Its fast
+// path keeps panel it+1 in registers across panel it's MFMA loop: the loads
+// are issued before the loop and the LDS writes after it, into buffer q^1,
+// which was last read in panel it-1 and is protected by that panel's closing
+// barrier; the barrier that closes panel it publishes it.  No barrier is
+// added.
 template <int BM, int BN, int BK, int WM, int WN, int MM, bool ABFT,
-          bool INJECT, int OCC = 2, bool LOG = false>
+          bool INJECT, int OCC = 2, bool LOG = false, bool TA = false,
+          bool TB = false>
 __global__ __launch_bounds__(
     (tile_geom<BM, BN, BK, WM, WN, MM, ABFT>::THREADS),
     OCC) void sgemm_mfma_ragged(int M, int N, int K, int lda, int ldb, int ldc,
@@ -157,20 +312,72 @@ __global__ __launch_bounds__(
   const bool a_fast = (fast & RAGGED_FAST_A) && im0 + BM <= M;
   const bool b_fast = (fast & RAGGED_FAST_B) && jn0 + BN <= N;
 
+  using StA = stage_operand_t<BM, BK, THREADS>;
+  using StB = stage_operand_t<BN, BK, THREADS>;
+  typename StA::regs ra;  // a transposed operand's next panel (fast path)
+  typename StB::regs rb;
+
+  // Both operands transposed: A's registers are written to LDS half way
+  // through the MFMA loop and B's are loaded only then, so that the two sets
+  // are never live together (with both held across the loop the fused huge
+  // kernels spill, docs/ABLATION.md section 16).
+  constexpr bool SPLIT = TA && TB;
+
+  // Starts the staging of panel k0 into buffer q.  A transposed operand on
+  // its fast path is only loaded into ra / rb: the caller writes it to LDS
+  // with stage_mid / stage_finish once buffer q may be overwritten.
+  auto load_b_t = [&](int k0) __attribute__((always_inline)) {
+    if (b_fast && k0 + BK <= K) StB::load(rb, B, ldb, jn0, k0, tid);
+  };
+  auto store_a_t = [&](int q, int k0) __attribute__((always_inline)) {
+    if (a_fast && k0 + BK <= K) StA::store(ra, &lds[q * BUF], tid);
+  };
   auto stage = [&](int q, int k0) __attribute__((always_inline)) {
     const bool k_full = k0 + BK <= K;
-    if (a_fast && k_full)
-      stage_operand<BM, BK, THREADS>(&lds[q * BUF], A, lda, im0, k0, tid,
-                                     wave);
-    else
-      stage_operand_guarded<BM, BK, THREADS>(&lds[q * BUF], A, lda, M, K, im0,
-                                             k0, tid, wave);
-    if (b_fast && k_full)
-      stage_operand<BN, BK, THREADS>(&lds[q * BUF + BM * BK], B, ldb, jn0, k0,
-                                     tid, wave);
-    else
-      stage_operand_guarded<BN, BK, THREADS>(&lds[q * BUF + BM * BK], B, ldb,
-                                             N, K, jn0, k0, tid, wave);
+    if constexpr (TA) {
+      if (a_fast && k_full)
+        StA::load(ra, A, lda, im0, k0, tid);
+      else
+        stage_operand_guarded_t<BM, BK, THREADS>(&lds[q * BUF], A, lda, M, K,
+                                                 im0, k0, tid, wave);
+    } else {
+      if (a_fast && k_full)
+        stage_operand<BM, BK, THREADS>(&lds[q * BUF], A, lda, im0, k0, tid,
+                                       wave);
+      else
+        stage_operand_guarded<BM, BK, THREADS>(&lds[q * BUF], A, lda, M, K,
+                                               im0, k0, tid, wave);
+    }
+    if constexpr (TB) {
+      if constexpr (!SPLIT) load_b_t(k0);
+      if (!(b_fast && k_full))
+        stage_operand_guarded_t<BN, BK, THREADS>(&lds[q * BUF + BM * BK], B,
+                                                 ldb, N, K, jn0, k0, tid,
+                                                 wave);
+    } else {
+      if (b_fast && k_full)
+        stage_operand<BN, BK, THREADS>(&lds[q * BUF + BM * BK], B, ldb, jn0,
+                                       k0, tid, wave);
+      else
+        stage_operand_guarded<BN, BK, THREADS>(&lds[q * BUF + BM * BK], B, ldb,
+                                               N, K, jn0, k0, tid, wave);
+    }
+  };
+  auto stage_mid = [&](int q, int k0) __attribute__((always_inline)) {
+    if constexpr (SPLIT) {
+      store_a_t(q, k0);
+      load_b_t(k0);
+    }
+  };
+  auto stage_finish = [&](int q, int k0) __attribute__((always_inline)) {
+    if constexpr (TA || TB) {
+      if constexpr (TA && !SPLIT) store_a_t(q, k0);
+      if constexpr (TB) {
+        if (b_fast && k0 + BK <= K)
+          StB::store(rb, &lds[q * BUF + BM * BK], tid);
+      }
+      FT_PARA_SYNC();
+    }
   };
 
   // This wave's WM-row band of A.  The workspace holds ceil(M/WM) bands; a
@@ -193,6 +400,8 @@ __global__ __launch_bounds__(
 
   // ---- main K loop: sgemm_mfma's, over ceil(K/BK) panels ----
   stage(0, 0);
+  stage_mid(0, 0);
+  stage_finish(0, 0);
   if constexpr (ABFT) stage_strip(0, 0);  // window 0 (panels 0..PPS-1)
   FT_PARA_SYNC();
   __syncthreads();  // drains in-flight glds
@@ -230,6 +439,10 @@ __global__ __launch_bounds__(
       float bv[DEFER ? NKK : 1][FN];
 #pragma unroll
       for (int kk = 0; kk < NKK; ++kk) {
+        if constexpr (SPLIT) {
+          if (kk == NKK / 2 && it + 1 < niter)
+            stage_mid(q ^ 1, (it + 1) * BK);
+        }
         const int kloc = kk * KSTEP + sub;
         float a[FM], b[FN];
 #pragma unroll
@@ -254,6 +467,7 @@ __global__ __launch_bounds__(
           for (int fn = 0; fn < FN; ++fn)
             acc[fm][fn] = T::mma(a[fm], b[fn], acc[fm][fn]);
       }
+      if (it + 1 < niter) stage_finish(q ^ 1, (it + 1) * BK);
       __syncthreads();
       if constexpr (DEFER) {
 #pragma unroll
@@ -313,15 +527,18 @@ __global__ __launch_bounds__(
 }
 
 // Ragged launch of one tier: any M, N, K >= 1 on a ceil(M/BM) x ceil(N/BN)
-// grid of sgemm_mfma_ragged.  g.lda / ldb / ldc of 0 mean packed (M, N, M).
+// grid of sgemm_mfma_ragged.  g.lda / ldb / ldc of 0 mean packed (M, N, M; K
+// for a transposed operand).  TA / TB must equal g.transA / g.transB:
+// sgemm_tier_launch picks the translation unit that holds the combination.
 // The workspace has one row per WM-row band of A, the last band partial.
 // No allocation and no sync, so the launch can be captured.
-template <int BM, int BN, int BK, int BKF, int WM, int WN, int MM>
+template <int BM, int BN, int BK, int BKF, int WM, int WN, int MM,
+          bool TA = false, bool TB = false>
 hipError_t launch_tier_ragged(const GemmArgs& g) {
   const bool abft = g.abft, inject = g.inject;
   const int M = g.M, N = g.N, K = g.K;
-  const int lda = g.lda ? g.lda : M, ldb = g.ldb ? g.ldb : N,
-            ldc = g.ldc ? g.ldc : M;
+  const int lda = g.lda ? g.lda : (TA ? K : M),
+            ldb = g.ldb ? g.ldb : (TB ? K : N), ldc = g.ldc ? g.ldc : M;
   const auto fast_ok = [](const void* p, int ld) {
     return ((uintptr_t)p & 15) == 0 && ld % 4 == 0;
   };
@@ -338,8 +555,15 @@ hipError_t launch_tier_ragged(const GemmArgs& g) {
     cs.sstr = abft_sstr(K);
     cs.SA = g.ws;
     RoctxRange rr("abft_encode_segsum_ragged");
-    hipLaunchKernelGGL((segsum_ragged_kernel<WM>), dim3(cs.sstr), dim3(256), 0,
-                       g.stream, M, K, lda, cs.sstr, g.A, g.ws);
+    if constexpr (TA) {
+      const int kblocks = (cs.sstr + 255) / 256;
+      hipLaunchKernelGGL((segsum_ragged_t_kernel<WM>),
+                         dim3((M + WM - 1) / WM, kblocks < 1024 ? kblocks : 1024),
+                         dim3(256), 0, g.stream, M, K, lda, cs.sstr, g.A, g.ws);
+    } else {
+      hipLaunchKernelGGL((segsum_ragged_kernel<WM>), dim3(cs.sstr), dim3(256),
+                         0, g.stream, M, K, lda, cs.sstr, g.A, g.ws);
+    }
   }
   RoctxRange rr_main(abft ? (inject ? "ft_sgemm_ragged_abft_inject"
                                     : "ft_sgemm_ragged_abft")
@@ -347,11 +571,12 @@ hipError_t launch_tier_ragged(const GemmArgs& g) {
   const FaultLog flog = attached_log(abft, g.log);
   const auto kfn = select_variant(
       abft, inject, flog.counters != nullptr,
-      &sgemm_mfma_ragged<BM, BN, BK, WM, WN, MM, false, false>,
+      &sgemm_mfma_ragged<BM, BN, BK, WM, WN, MM, false, false, 2, false, TA,
+                         TB>,
       [](auto inj, auto lg) {
         return &sgemm_mfma_ragged<BM, BN, BKF, WM, WN, MM, true,
                                   decltype(inj)::value, 2,
-                                  decltype(lg)::value>;
+                                  decltype(lg)::value, TA, TB>;
       });
   hipLaunchKernelGGL(kfn, grid, block, 0, g.stream, M, N, K, lda, ldb, ldc,
                      fast, g.A, g.B, g.C, g.alpha, g.beta, stride, stride,

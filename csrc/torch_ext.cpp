@@ -189,14 +189,16 @@ void sgemm_batched(int64_t tier, bool abft, bool inject, at::Tensor a,
               counters, events, /*log_batch=*/c.size(0));
 }
 
-// Layout of a ragged call, read off the tensors into the M, N, K, ragged and
-// leading-dimension fields of a GemmArgs: a (K,M), b (K,N), c (N,M), any
-// sizes >= 1, unit inner stride.  The row stride is the column-major leading
-// dimension; a one-row tensor's is its width.  That it must not be shorter
-// than the row is gemm_args_error's to say (ops.ragged_layout is the Python
-// mirror that raises ValueError before a call gets here).
+// Layout of a ragged call, read off the tensors into the M, N, K, ragged,
+// transpose and leading-dimension fields of a GemmArgs: a (K,M), b (K,N),
+// c (N,M), any sizes >= 1, unit inner stride; with trans_a, a is (M,K), with
+// trans_b, b is (N,K).  The row stride is the leading dimension; a one-row
+// tensor's is its width.  That it must not be shorter than the row is
+// gemm_args_error's to say (ops.ragged_layout is the Python mirror that
+// raises ValueError before a call gets here).
 ftsgemm::GemmArgs check_ragged_inputs(const at::Tensor& a, const at::Tensor& b,
-                                      const at::Tensor& c) {
+                                      const at::Tensor& c, bool trans_a,
+                                      bool trans_b) {
   const char* nm = "ft_sgemm_ragged";
   TORCH_CHECK(a.is_cuda() && b.is_cuda() && c.is_cuda(), nm,
               ": tensors must be on a GPU device");
@@ -208,9 +210,12 @@ ftsgemm::GemmArgs check_ragged_inputs(const at::Tensor& a, const at::Tensor& b,
               nm, ": fp32 only (SGEMM)");
   TORCH_CHECK(a.dim() == 2 && b.dim() == 2 && c.dim() == 2, nm,
               ": 2-D tensors a (K,M), b (K,N), c (N,M) expected");
-  const int64_t M = a.size(1), N = b.size(1), K = a.size(0);
+  const int64_t M = a.size(trans_a ? 0 : 1), N = b.size(trans_b ? 0 : 1),
+                K = a.size(trans_a ? 1 : 0);
   TORCH_CHECK(M >= 1 && N >= 1 && K >= 1, nm, ": empty matrix");
-  TORCH_CHECK(b.size(0) == K, nm, ": a is (K,M) and b must be (K,N)");
+  TORCH_CHECK(b.size(trans_b ? 1 : 0) == K, nm,
+              ": a and b disagree on K (a is (K,M), or (M,K) with trans_a; b "
+              "is (K,N), or (N,K) with trans_b)");
   TORCH_CHECK(c.size(0) == N && c.size(1) == M, nm,
               ": c must be (N,M) for column-major MxN");
   TORCH_CHECK(M <= INT32_MAX && N <= INT32_MAX && K <= INT32_MAX - 64, nm,
@@ -228,20 +233,23 @@ ftsgemm::GemmArgs check_ragged_inputs(const at::Tensor& a, const at::Tensor& b,
   ftsgemm::GemmArgs g{};
   g.M = (int)M, g.N = (int)N, g.K = (int)K;
   g.ragged = true;
+  g.transA = trans_a, g.transB = trans_b;
   g.lda = ld(a, "a"), g.ldb = ld(b, "b"), g.ldc = ld(c, "c");
   return g;
 }
 
-// Ragged twin of sgemm: any M, N, K and row-strided operands.  Fault log as
-// sgemm's.
+// Ragged twin of sgemm: any M, N, K and row-strided operands, either of
+// which may be given transposed.  Fault log as sgemm's.
 void sgemm_ragged(int64_t tier, bool abft, bool inject, at::Tensor a,
                   at::Tensor b, at::Tensor c, double alpha, double beta,
                   double tau, double inj_mag, int64_t verify_windows,
                   c10::optional<at::Tensor> counters,
-                  c10::optional<at::Tensor> events) {
-  launch_gemm("ft_sgemm_ragged", tier, check_ragged_inputs(a, b, c), abft,
-              inject, a, b, c, alpha, beta, tau, inj_mag, verify_windows,
-              counters, events, /*log_batch=*/0);
+                  c10::optional<at::Tensor> events, bool trans_a,
+                  bool trans_b) {
+  launch_gemm("ft_sgemm_ragged", tier,
+              check_ragged_inputs(a, b, c, trans_a, trans_b), abft, inject, a,
+              b, c, alpha, beta, tau, inj_mag, verify_windows, counters,
+              events, /*log_batch=*/0);
 }
 
 int64_t ragged_workspace_floats(int64_t tier, int64_t M, int64_t N,
@@ -430,7 +438,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("tier"), py::arg("abft"), py::arg("inject"), py::arg("a"),
         py::arg("b"), py::arg("c"), py::arg("alpha"), py::arg("beta"),
         py::arg("tau"), py::arg("inj_mag"), py::arg("verify_windows"),
-        py::arg("counters") = py::none(), py::arg("events") = py::none());
+        py::arg("counters") = py::none(), py::arg("events") = py::none(),
+        py::arg("trans_a") = false, py::arg("trans_b") = false);
   m.def("ragged_workspace_floats", &ragged_workspace_floats,
         "ABFT scratch floats a fused sgemm_ragged call allocates");
   m.def("rocblas_sgemm", &rocblas_sgemm_nt, "rocBLAS oracle SGEMM");

@@ -72,5 +72,38 @@ int main() {
   }
   hipDeviceSynchronize();
   printf("ragged fused-ABFT GEMM done\n");
+
+  // a linear layer's forward product, y (tokens x out) = x W^T, read in
+  // place: both operands are row-major with K = in as the inner dimension,
+  // which is transA and transB of a ragged launch (A = W, out x in, B = x,
+  // tokens x in, both with leading dimension in)
+  const int tokens = 1000, in = 515, out = 777;
+  ftsgemm::GemmArgs gt{/*abft=*/true, /*inject=*/true, out, tokens, in, dA,
+                       dB, dC, 1.f, 0.f, 9500.f, 10000.f, 20, ws};
+  gt.ragged = true;
+  gt.transA = gt.transB = true;
+  gt.lda = gt.ldb = in;
+  if (ftsgemm::sgemm_abft_workspace_floats(FT_TIER_ID_large, gt) > wsf)
+    return 1;
+  err = ftsgemm::sgemm_tier_launch(FT_TIER_ID_large, gt);
+  if (err != hipSuccess) {
+    fprintf(stderr, "transposed launch failed: %s\n", hipGetErrorString(err));
+    return 1;
+  }
+  hipDeviceSynchronize();
+  printf("transposed ragged fused-ABFT GEMM done\n");
+
+  // the transposes belong to ragged launches: on a tiled one the flag is
+  // refused by the launch rules and nothing is launched
+  ftsgemm::GemmArgs gx = g;
+  gx.inject = false;
+  gx.transA = true;
+  const char* why = ftsgemm::gemm_args_error(FT_TIER_ID_huge, gx);
+  err = ftsgemm::sgemm_tier_launch(FT_TIER_ID_huge, gx);
+  if (!why || err != hipErrorInvalidValue) {
+    fprintf(stderr, "a transposed tiled launch was not refused\n");
+    return 1;
+  }
+  printf("transposed tiled launch refused: %s\n", why);
   return 0;
 }

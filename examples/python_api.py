@@ -88,5 +88,19 @@ block_row_sgemm(a, b, c, panel_k=1024,
                 batched_gemm_fn=lambda ap, bs, cs, al, be:
                     ops.ft_sgemm_batched("huge", ap, bs, cs, al, be))
 
+# 8. transposed operands: a linear layer's y = x @ W^T has both operands
+#    row-major with K inner — trans_a / trans_b read them in place (ragged
+#    entries only), with the bits of the call on .t().contiguous() copies.
+x = torch.rand((1000, 515), device="cuda")        # (tokens, in)  = b as (N, K)
+w = torch.rand((777, 515), device="cuda")         # (out, in)     = a as (M, K)
+y = torch.empty((1000, 777), device="cuda")       # (tokens, out) = c   (N, M)
+ops.ft_sgemm_ragged("large", w, x, y, inject=True, trans_a=True, trans_b=True)
+
+#    the same as a differentiable layer: forward, grad_x and grad_weight all
+#    run the fused-ABFT kernel with no operand copy; one report for all three
+lin = ops.FTLinear(515, 777, device="cuda", inject=True, report=report)
+lin(x.requires_grad_()).sum().backward()
+print("linear layer corrected faults:", report.read().corrected)
+
 torch.cuda.synchronize()
 print("examples OK")

@@ -45,18 +45,19 @@ def tier_index(tier: str) -> int:
 
 
 def _launch(entry: str, tier: str, a, b, c, alpha, beta, fused=None,
-            report=None):
+            report=None, **kw):
     """The one call into the binding `entry` (sgemm, sgemm_batched or
     sgemm_ragged): plain when fused is None, otherwise the fused-ABFT twin
     with fused = (inject, tau, inj_mag, verify_windows) and the optional
-    fault report."""
+    fault report.  kw: the entry's own keywords (sgemm_ragged's trans_a,
+    trans_b)."""
     abft = fused is not None
     inject, tau, inj_mag, verify_windows = fused if abft else (False, 0.0,
                                                                0.0, 20)
     log = (None, None) if report is None else (report.counters, report.events)
     getattr(_require_ext(), entry)(tier_index(tier), abft, inject, a, b, c,
                                    alpha, beta, tau, inj_mag, verify_windows,
-                                   *log)
+                                   *log, **kw)
     return c
 
 
@@ -181,17 +182,19 @@ def ft_sgemm_batched(tier: str, a: torch.Tensor, b: torch.Tensor,
                    (inject, tau, inj_mag, verify_windows), report)
 
 
-def ragged_layout(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor):
+def ragged_layout(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
+                  trans_a: bool = False, trans_b: bool = False):
     """Validate the operands of a ragged call and return
     (m, n, k, lda, ldb, ldc), the leading dimensions in floats.  Runs on any
     device: the CPU-runnable mirror of the launch rules, which the C++ side
     states once, in gemm_args_error (csrc/dispatch.hip).
 
-    a is (K, M), b is (K, N), c is (N, M), fp32, any sizes >= 1.  The inner
-    stride must be 1 and the row stride at least the row width, so packed
-    tensors and row-strided views (x[k0:k1, m0:m1]) pass without a copy; the
-    row stride is the column-major leading dimension, and a one-row tensor's
-    is its width.  No alignment beyond fp32 is asked for.  c's rows must not
+    a is (K, M), b is (K, N), c is (N, M), fp32, any sizes >= 1.  With
+    trans_a, a is given transposed, as (M, K); with trans_b, b is (N, K).
+    The inner stride must be 1 and the row stride at least the row width, so
+    packed tensors and row-strided views (x[r0:r1, c0:c1]) pass without a
+    copy; the row stride is the leading dimension, and a one-row tensor's is
+    its width.  No alignment beyond fp32 is asked for.  c's rows must not
     overlap.  Raises ValueError."""
     def err(msg):
         raise ValueError(f"sgemm_ragged: {msg}")
@@ -201,10 +204,11 @@ def ragged_layout(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor):
             err(f"{name} must be 2-D, got {tuple(x.shape)}")
         if x.dtype != torch.float32:
             err(f"{name} must be float32")
-    k, m = a.shape
-    n = b.shape[1]
-    if b.shape[0] != k or tuple(c.shape) != (n, m):
-        err(f"a (K, M) = {tuple(a.shape)}, b (K, N) = {tuple(b.shape)} and "
+    m, k = a.shape if trans_a else a.shape[::-1]
+    n, kb = b.shape if trans_b else b.shape[::-1]
+    if kb != k or tuple(c.shape) != (n, m):
+        err(f"a {'(M, K)' if trans_a else '(K, M)'} = {tuple(a.shape)}, "
+            f"b {'(N, K)' if trans_b else '(K, N)'} = {tuple(b.shape)} and "
             f"c (N, M) = {tuple(c.shape)} disagree")
     if min(m, n, k) < 1:
         err("empty matrix")
@@ -224,32 +228,43 @@ def ragged_layout(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor):
 
 
 def sgemm_ragged(tier: str, a: torch.Tensor, b: torch.Tensor,
-                 c: torch.Tensor, alpha: float = 1.0,
-                 beta: float = 0.0) -> torch.Tensor:
+                 c: torch.Tensor, alpha: float = 1.0, beta: float = 0.0, *,
+                 trans_a: bool = False, trans_b: bool = False
+                 ) -> torch.Tensor:
     """Plain SGEMM for any M, N, K >= 1 and row-strided operands (layout
     rules in ragged_layout), on the ragged twin of `tier`'s classic kernel:
     ceil tile counts, out-of-range operand elements staged as zeros, only the
     M x N window of c written.  On a shape the tile divides the result has
     the bits of sgemm with the classic (non-stream-K) decomposition.
-    In-place on c."""
-    ragged_layout(a, b, c)
-    return _launch("sgemm_ragged", tier, a, b, c, alpha, beta)
+    In-place on c.
+
+    trans_a / trans_b: that operand is given transposed, a as (M, K), b as
+    (N, K), and read in place: c = alpha * b @ a^T + beta * c for both, the
+    form of a linear layer.  The result has the bits of the untransposed
+    call on x.t().contiguous()."""
+    ragged_layout(a, b, c, trans_a, trans_b)
+    return _launch("sgemm_ragged", tier, a, b, c, alpha, beta,
+                   trans_a=trans_a, trans_b=trans_b)
 
 
 def ft_sgemm_ragged(tier: str, a: torch.Tensor, b: torch.Tensor,
                     c: torch.Tensor, alpha: float = 1.0, beta: float = 0.0,
                     inject: bool = True, tau: float = ERR_BOUND,
                     inj_mag: float = ERROR_INJECT, verify_windows: int = 20,
-                    report: FaultReport | None = None) -> torch.Tensor:
+                    report: FaultReport | None = None, *,
+                    trans_a: bool = False, trans_b: bool = False
+                    ) -> torch.Tensor:
     """Fused-ABFT SGEMM for any M, N, K >= 1 and row-strided operands:
     ft_sgemm's in-kernel verify / locate / correct, injector self-test and
-    fault report without a tile fit; arguments as ft_sgemm, layout as
-    sgemm_ragged.  The injector keeps its per-block rule, so in an edge tile
-    a victim may lie in the padding: it is corrected like any other and
-    reported with its padded coordinates (FaultReport)."""
-    ragged_layout(a, b, c)
+    fault report without a tile fit; arguments as ft_sgemm, layout and
+    trans_a / trans_b as sgemm_ragged.  The injector keeps its per-block
+    rule, so in an edge tile a victim may lie in the padding: it is corrected
+    like any other and reported with its padded coordinates (FaultReport).
+    Transposition moves no fault."""
+    ragged_layout(a, b, c, trans_a, trans_b)
     return _launch("sgemm_ragged", tier, a, b, c, alpha, beta,
-                   (inject, tau, inj_mag, verify_windows), report)
+                   (inject, tau, inj_mag, verify_windows), report,
+                   trans_a=trans_a, trans_b=trans_b)
 
 
 def rocblas_sgemm(a, b, c, alpha: float = 1.0, beta: float = 0.0):
@@ -526,3 +541,6 @@ def torch_reference_batched(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
     a3, b3 = (x if x.dim() == 3 else x.unsqueeze(0).expand(batch, -1, -1)
               for x in (a, b))
     return alpha * torch.bmm(b3.transpose(1, 2), a3) + beta * c
+
+
+from .linear import FTLinear, ft_linear  # noqa: E402,F401
