@@ -19,7 +19,11 @@ namespace ftsgemm {
   hipError_t launch_tier_ragged_##name(const GemmArgs& g);    \
   hipError_t launch_tier_ragged_tn_##name(const GemmArgs& g); \
   hipError_t launch_tier_ragged_nt_##name(const GemmArgs& g); \
-  hipError_t launch_tier_ragged_tt_##name(const GemmArgs& g);
+  hipError_t launch_tier_ragged_tt_##name(const GemmArgs& g); \
+  hipError_t launch_tier_ragged_batched_##name(const GemmArgs& g);    \
+  hipError_t launch_tier_ragged_batched_tn_##name(const GemmArgs& g); \
+  hipError_t launch_tier_ragged_batched_nt_##name(const GemmArgs& g); \
+  hipError_t launch_tier_ragged_batched_tt_##name(const GemmArgs& g);
 FT_TIER_LIST(FT_DECL)
 #undef FT_DECL
 
@@ -32,6 +36,7 @@ struct TierRow {
   hipError_t (*launch_batched)(const GemmArgs&);  // batch > 1
   // g.ragged, indexed by transA + 2 * transB: one translation unit each
   hipError_t (*launch_ragged[4])(const GemmArgs&);
+  hipError_t (*launch_ragged_batched[4])(const GemmArgs&);  // and batch > 1
   int bm, bn, bk, wm;
 };
 const TierRow kTiers[FT_N_TIERS] = {
@@ -40,6 +45,10 @@ const TierRow kTiers[FT_N_TIERS] = {
    launch_tier_batched_##name,                                      \
    {launch_tier_ragged_##name, launch_tier_ragged_tn_##name,        \
     launch_tier_ragged_nt_##name, launch_tier_ragged_tt_##name},    \
+   {launch_tier_ragged_batched_##name,                              \
+    launch_tier_ragged_batched_tn_##name,                           \
+    launch_tier_ragged_batched_nt_##name,                           \
+    launch_tier_ragged_batched_tt_##name},                          \
    BM, BN, BK, WM},
     FT_TIER_LIST(FT_ROW)
 #undef FT_ROW
@@ -74,7 +83,7 @@ const char* gemm_args_error(int tier, const GemmArgs& g) {
   if ((g.transA || g.transB) && !g.ragged)
     return "transA / transB need a ragged launch";
   if (g.ragged) {
-    if (g.batch != 1) return "a ragged launch is one product (batch == 1)";
+    if (g.batch < 1 || g.batch > kMaxGridYZ) return "batch outside 1..65535";
     // a leading dimension may pad its rows, never cut them; a transposed
     // operand's rows run along k
     if ((g.lda && g.lda < (g.transA ? g.K : g.M)) ||
@@ -83,6 +92,21 @@ const char* gemm_args_error(int tier, const GemmArgs& g) {
     if (ptrs & 3) return "A, B, C and ws must be 4-byte aligned";
     if ((g.N + t->bn - 1) / t->bn > kMaxGridYZ)
       return "N needs more than 65535 tile columns";
+    if (g.batch > 1) {
+      // blockIdx.z carries the entry.  Any stride: the kernel settles the
+      // 16-B paths per entry (ft_ragged.hpp), so 4-B alignment is enough.
+      if (g.strideA < 0 || g.strideB < 0)
+        return "batch strides of A and B must be >= 0";
+      // C entries are written: disjoint, or interleaved within a row of ldc
+      // (heads inside a (tokens, heads*dim) tensor)
+      const long long ldc = g.ldc ? g.ldc : g.M;
+      const bool disjoint = g.strideC >= (g.N - 1) * ldc + g.M;
+      const bool interleaved =
+          g.strideC >= g.M && (g.batch - 1) * g.strideC + g.M <= ldc;
+      if (!disjoint && !interleaved)
+        return "C entries overlap (strideC >= (N-1)*ldc + M, or strideC >= M "
+               "and (batch-1)*strideC + M <= ldc)";
+    }
     return nullptr;
   }
   if (!sgemm_tier_supported(tier, g.M, g.N, g.K))
@@ -104,8 +128,10 @@ const char* gemm_args_error(int tier, const GemmArgs& g) {
 hipError_t sgemm_tier_launch(int tier, const GemmArgs& g) {
   if (gemm_args_error(tier, g)) return hipErrorInvalidValue;
   const TierRow& t = kTiers[tier];
-  if (g.ragged)
-    return t.launch_ragged[(g.transA ? 1 : 0) + (g.transB ? 2 : 0)](g);
+  if (g.ragged) {
+    const int tr = (g.transA ? 1 : 0) + (g.transB ? 2 : 0);
+    return g.batch > 1 ? t.launch_ragged_batched[tr](g) : t.launch_ragged[tr](g);
+  }
   return g.batch > 1 ? t.launch_batched(g) : t.launch(g);
 }
 

@@ -33,11 +33,16 @@ namespace ftsgemm {
 // (FT_SGEMM_STREAMK has no effect on it); batch == 1 is the single launch and
 // ignores the strides.
 //
-// ragged lifts the tile fit of a single product: any M, N, K >= 1, leading
-// dimensions lda / ldb / ldc (0 = packed), base pointers with only fp32
-// alignment.  The ragged twin of the classic kernel runs (ft_ragged.hpp) on
-// ceil tile counts.  A fault injected into an edge tile's padding is logged
-// with its padded coordinates (fault_log.h).
+// ragged lifts the tile fit: any M, N, K >= 1, leading dimensions lda / ldb
+// / ldc (0 = packed), base pointers with only fp32 alignment.  The ragged
+// twin of the classic kernel runs (ft_ragged.hpp) on ceil tile counts.  A
+// fault injected into an edge tile's padding is logged with its padded
+// coordinates (fault_log.h).  ragged with batch > 1 is a strided batch of
+// such products in one launch: any strides (A's and B's >= 0, 0 = shared),
+// no alignment beyond fp32 for any entry, workspace and logs laid out as for
+// the tiled batch.  C's entries may be disjoint or interleaved within a row
+// of ldc (entry b's rows inside the rows of one wider matrix), never
+// overlapping.  ragged with batch == 1 is the single ragged launch.
 //
 // transA / transB (ragged launches only) take that operand transposed, i.e.
 // row-major: with transA, element (i, k) of the logical M x K matrix A is at

@@ -31,7 +31,26 @@
 // instantiations are the kernels as they were and keep their own translation
 // units; the others live in kernel_<tier>_ragged_{tn,nt,tt}.hip.
 //
-// Classic decomposition only: no stream-K, no batch.
+// Strided batches (template flag BATCHED, GemmArgs::batch > 1): the entry is
+// blockIdx.z and, as in sgemm_mfma, only the prologue knows.  It moves A, B,
+// C, SA and the fault log to entry z by wave-uniform 64-bit offsets
+// (BatchStrides); everything below it is the single-product kernel, so entry
+// z has the bits of the single launch on its views.  No stride has to be a
+// multiple of 4, so entry z's base X + z*strideX can be misaligned where
+// entry 0's is not.  The fast bits are therefore settled per entry: the host
+// sets a bit from the leading dimension alone (ld % 4 == 0) and the prologue
+// clears it unless the entry's own moved pointer is 16-B aligned.  That is
+// two scalar ANDs per operand, it keeps the 16-B paths for every entry that
+// can take them (with an odd stride, every fourth), and the other way —
+// clearing the bit for the whole launch — would put every entry of such a
+// batch on the 4-B paths.  Either is correct: the result does not depend on
+// which staging ran.  The segment-sum kernels take the entry as one more grid
+// dimension and test `vec` on the entry's own column pointer.  The
+// BATCHED = false instantiations never look at the strides and keep their
+// translation units; the batched ones live in
+// kernel_<tier>_ragged_batched_{nn,tn,nt,tt}.hip.
+//
+// Classic decomposition only: no stream-K.
 
 #pragma once
 
@@ -50,6 +69,16 @@ enum RaggedFast {
   RAGGED_FAST_B = 2,  // B 16-B aligned and ldb % 4 == 0
   RAGGED_FAST_C = 4,  // C 16-B aligned and ldc % 4 == 0
 };
+
+// The bits of `fast` that entry pointers A, B, C still allow (batched
+// prologue; workgroup-uniform).
+__device__ __attribute__((always_inline)) inline int ragged_fast_entry(
+    int fast, const float* A, const float* B, const float* C) {
+  if ((uintptr_t)A & 15) fast &= ~RAGGED_FAST_A;
+  if ((uintptr_t)B & 15) fast &= ~RAGGED_FAST_B;
+  if ((uintptr_t)C & 15) fast &= ~RAGGED_FAST_C;
+  return fast;
+}
 
 // Guarded twin of stage_operand: the same ROWS x BK panel into the same LDS
 // layout ([k][row], element f = k*ROWS + row), 4 B per lane.  A lane whose row
@@ -178,10 +207,19 @@ __device__ __attribute__((always_inline)) inline void segsum_rows4(
 // Block k in [K, sstr) writes zeros: the last panel and the last 64-k strip
 // window read those entries, and a stale NaN there times a zero B would
 // poison the checksum.
-template <int SEG>
+// BATCHED: launched on (sstr, nA); blockIdx.y picks the matrix (strideA floats
+// apart) and its copy of the workspace layout (strideS floats apart).  The
+// sums, their order, the zero fill and the vec test (on the entry's own
+// column) are the unbatched kernel's, which never looks at the strides.
+template <int SEG, bool BATCHED = false>
 __global__ __launch_bounds__(256) void segsum_ragged_kernel(
     int M, int K, int lda, int sstr, const float* __restrict__ A,
-    float* __restrict__ S) {
+    float* __restrict__ S, long long strideA, long long strideS) {
+  if constexpr (BATCHED) {
+    const long long z = blockIdx.y;
+    A += z * strideA;
+    S += z * strideS;
+  }
   const int k = blockIdx.x;
   const int tid = threadIdx.x;
   if (k >= K) {
@@ -247,10 +285,16 @@ __device__ __attribute__((always_inline)) inline void segsum_t_tree(
 // the same workspace, the same zero fill of [K, sstr) and the same bits.
 // Threads run along k, so the reads are coalesced; blockIdx.x is the band and
 // each thread walks its band's SEG rows.  Rows >= M contribute exact zeros.
-template <int SEG>
+// BATCHED: blockIdx.z picks the matrix and its workspace copy, as above.
+template <int SEG, bool BATCHED = false>
 __global__ __launch_bounds__(256) void segsum_ragged_t_kernel(
     int M, int K, int lda, int sstr, const float* __restrict__ A,
-    float* __restrict__ S) {
+    float* __restrict__ S, long long strideA, long long strideS) {
+  if constexpr (BATCHED) {
+    const long long z = blockIdx.z;
+    A += z * strideA;
+    S += z * strideS;
+  }
   const int band = blockIdx.x;
   float* out = S + (size_t)band * 2 * sstr;
   for (int k = blockIdx.y * 256 + threadIdx.x; k < sstr;
@@ -275,9 +319,12 @@ __global__ __launch_bounds__(256) void segsum_ragged_t_kernel(
 // which was last read in panel it-1 and is protected by that panel's closing
 // barrier; the barrier that closes panel it publishes it.  No barrier is
 // added.
+//
+// BATCHED: one product per blockIdx.z; the prologue moves the pointers and the
+// fault log to the entry and settles the entry's fast bits (header comment).
 template <int BM, int BN, int BK, int WM, int WN, int MM, bool ABFT,
           bool INJECT, int OCC = 2, bool LOG = false, bool TA = false,
-          bool TB = false>
+          bool TB = false, bool BATCHED = false>
 __global__ __launch_bounds__(
     (tile_geom<BM, BN, BK, WM, WN, MM, ABFT>::THREADS),
     OCC) void sgemm_mfma_ragged(int M, int N, int K, int lda, int ldb, int ldc,
@@ -286,8 +333,20 @@ __global__ __launch_bounds__(
                                 float* __restrict__ C, float alpha, float beta,
                                 int verify_iters, int inject_stride, float tau,
                                 float inj_mag, const float* __restrict__ SA,
-                                int sstr, FaultLog flog) {
+                                int sstr, FaultLog flog, BatchStrides bs) {
   using G = tile_geom<BM, BN, BK, WM, WN, MM, ABFT>;
+  if constexpr (BATCHED) {
+    const long long z = blockIdx.z;
+    A += z * bs.A;
+    B += z * bs.B;
+    C += z * bs.C;
+    fast = ragged_fast_entry(fast, A, B, C);
+    if constexpr (ABFT) SA += z * bs.SA;
+    if constexpr (LOG) {
+      flog.counters += z * FLOG_N_COUNTERS;
+      flog.events += z * flog.capacity * FLOG_EVENT_DWORDS;
+    }
+  }
   using T = typename G::T;
   constexpr int KSTEP = G::KSTEP, THREADS = G::THREADS, FM = G::FM,
                 FN = G::FN, BUF = G::BUF, STRIP_OFF = G::STRIP_OFF,
@@ -532,55 +591,75 @@ __global__ __launch_bounds__(
 // sgemm_tier_launch picks the translation unit that holds the combination.
 // The workspace has one row per WM-row band of A, the last band partial.
 // No allocation and no sync, so the launch can be captured.
+//
+// BATCHED (g.batch > 1, instantiated in the _ragged_batched translation units
+// only): g.batch products on a ceil(M/BM) x ceil(N/BN) x batch grid, one
+// encode launch and one GEMM launch.  strideA == 0 shares A: it is encoded
+// once and every entry reads that workspace; otherwise g.ws holds g.batch
+// copies of the single-launch layout.  The fast bits then come from the
+// leading dimensions alone; the kernel settles them per entry.
 template <int BM, int BN, int BK, int BKF, int WM, int WN, int MM,
-          bool TA = false, bool TB = false>
+          bool TA = false, bool TB = false, bool BATCHED = false>
 hipError_t launch_tier_ragged(const GemmArgs& g) {
   const bool abft = g.abft, inject = g.inject;
   const int M = g.M, N = g.N, K = g.K;
   const int lda = g.lda ? g.lda : (TA ? K : M),
             ldb = g.ldb ? g.ldb : (TB ? K : N), ldc = g.ldc ? g.ldc : M;
   const auto fast_ok = [](const void* p, int ld) {
-    return ((uintptr_t)p & 15) == 0 && ld % 4 == 0;
+    return (BATCHED || ((uintptr_t)p & 15) == 0) && ld % 4 == 0;
   };
   const int fast = (fast_ok(g.A, lda) ? RAGGED_FAST_A : 0) |
                    (fast_ok(g.B, ldb) ? RAGGED_FAST_B : 0) |
                    (fast_ok(g.C, ldc) ? RAGGED_FAST_C : 0);
   const int bk_used = abft ? BKF : BK;
-  dim3 grid((M + BM - 1) / BM, (N + BN - 1) / BN);
+  dim3 grid((M + BM - 1) / BM, (N + BN - 1) / BN, BATCHED ? g.batch : 1);
   dim3 block(tile_geom<BM, BN, BK, WM, WN, MM, false>::THREADS);
   const int stride = window_stride((K + bk_used - 1) / bk_used,
                                    abft ? g.verify_windows : 1);
+  BatchStrides bs;
+  if constexpr (BATCHED) bs = {g.strideA, g.strideB, g.strideC, 0};
   Checksums cs;
   if (abft) {
     cs.sstr = abft_sstr(K);
     cs.SA = g.ws;
-    RoctxRange rr("abft_encode_segsum_ragged");
+    const int bands = (M + WM - 1) / WM;
+    const int nA = BATCHED && g.strideA != 0 ? g.batch : 1;
+    // one matrix's rows of the workspace (sgemm_abft_workspace_floats)
+    const long long ws_each = 2LL * bands * cs.sstr;
+    if constexpr (BATCHED) bs.SA = nA == 1 ? 0 : ws_each;
+    RoctxRange rr(BATCHED ? "abft_encode_segsum_ragged_batched"
+                          : "abft_encode_segsum_ragged");
     if constexpr (TA) {
       const int kblocks = (cs.sstr + 255) / 256;
-      hipLaunchKernelGGL((segsum_ragged_t_kernel<WM>),
-                         dim3((M + WM - 1) / WM, kblocks < 1024 ? kblocks : 1024),
-                         dim3(256), 0, g.stream, M, K, lda, cs.sstr, g.A, g.ws);
+      hipLaunchKernelGGL((segsum_ragged_t_kernel<WM, BATCHED>),
+                         dim3(bands, kblocks < 1024 ? kblocks : 1024, nA),
+                         dim3(256), 0, g.stream, M, K, lda, cs.sstr, g.A, g.ws,
+                         g.strideA, ws_each);
     } else {
-      hipLaunchKernelGGL((segsum_ragged_kernel<WM>), dim3(cs.sstr), dim3(256),
-                         0, g.stream, M, K, lda, cs.sstr, g.A, g.ws);
+      hipLaunchKernelGGL((segsum_ragged_kernel<WM, BATCHED>),
+                         dim3(cs.sstr, nA), dim3(256), 0, g.stream, M, K, lda,
+                         cs.sstr, g.A, g.ws, g.strideA, ws_each);
     }
   }
-  RoctxRange rr_main(abft ? (inject ? "ft_sgemm_ragged_abft_inject"
-                                    : "ft_sgemm_ragged_abft")
-                          : "sgemm_ragged_plain");
+  RoctxRange rr_main(
+      abft ? (inject ? (BATCHED ? "ft_sgemm_ragged_batched_abft_inject"
+                                : "ft_sgemm_ragged_abft_inject")
+                     : (BATCHED ? "ft_sgemm_ragged_batched_abft"
+                                : "ft_sgemm_ragged_abft"))
+           : (BATCHED ? "sgemm_ragged_batched_plain" : "sgemm_ragged_plain"));
   const FaultLog flog = attached_log(abft, g.log);
   const auto kfn = select_variant(
       abft, inject, flog.counters != nullptr,
       &sgemm_mfma_ragged<BM, BN, BK, WM, WN, MM, false, false, 2, false, TA,
-                         TB>,
+                         TB, BATCHED>,
       [](auto inj, auto lg) {
         return &sgemm_mfma_ragged<BM, BN, BKF, WM, WN, MM, true,
                                   decltype(inj)::value, 2,
-                                  decltype(lg)::value, TA, TB>;
+                                  decltype(lg)::value, TA, TB, BATCHED>;
       });
   hipLaunchKernelGGL(kfn, grid, block, 0, g.stream, M, N, K, lda, ldb, ldc,
                      fast, g.A, g.B, g.C, g.alpha, g.beta, stride, stride,
-                     g.tau, g.inj_mag, cs.SA, cs.sstr, flog);
+                     g.tau, g.inj_mag, cs.SA, cs.sstr, flog, bs);
   return hipGetLastError();
 }
 

@@ -75,7 +75,8 @@ ftsgemm::FaultLog attach_fault_log(const char* nm, bool abft, at::Device dev,
   return flog;
 }
 
-// The one body behind sgemm, sgemm_batched and sgemm_ragged.  `g` arrives
+// The one body behind sgemm, sgemm_batched, sgemm_ragged and
+// sgemm_ragged_batched.  `g` arrives
 // with the layout its entry read off the tensors (M, N, K and the batch or
 // ragged fields); this fills in the rest, attaches the fault log (log_batch
 // as attach_fault_log's batch), holds the call to the launch rules
@@ -260,6 +261,87 @@ int64_t ragged_workspace_floats(int64_t tier, int64_t M, int64_t N,
   return (int64_t)ftsgemm::sgemm_abft_workspace_floats((int)tier, g);
 }
 
+// Layout of a strided-batched ragged call, read off the tensors: a (B,K,M),
+// b (B,K,N), c (B,N,M), or a (B,M,K) with trans_a and b (B,N,K) with trans_b.
+// Per entry the rules of check_ragged_inputs: unit inner stride (or inner
+// size 1), the row stride is the leading dimension, a one-row tensor's is its
+// width.  The batch stride is whatever the tensor has; 0 (an expand()ed
+// operand) is allowed for a and b.  What a launch asks of the batch size, the
+// strides and C's entries is gemm_args_error's to say
+// (ops.ragged_batched_layout is the Python mirror).
+ftsgemm::GemmArgs check_ragged_batched_inputs(const at::Tensor& a,
+                                              const at::Tensor& b,
+                                              const at::Tensor& c,
+                                              bool trans_a, bool trans_b) {
+  const char* nm = "ft_sgemm_ragged_batched";
+  TORCH_CHECK(a.is_cuda() && b.is_cuda() && c.is_cuda(), nm,
+              ": tensors must be on a GPU device");
+  TORCH_CHECK(a.device() == b.device() && a.device() == c.device(), nm,
+              ": tensors must be on one device");
+  TORCH_CHECK(a.scalar_type() == at::kFloat &&
+                  b.scalar_type() == at::kFloat &&
+                  c.scalar_type() == at::kFloat,
+              nm, ": fp32 only (SGEMM)");
+  TORCH_CHECK(a.dim() == 3 && b.dim() == 3 && c.dim() == 3, nm,
+              ": 3-D tensors a (B,K,M), b (B,K,N), c (B,N,M) expected");
+  const int64_t batch = c.size(0), M = a.size(trans_a ? 1 : 2),
+                N = b.size(trans_b ? 1 : 2), K = a.size(trans_a ? 2 : 1);
+  TORCH_CHECK(a.size(0) == batch && b.size(0) == batch, nm,
+              ": a, b and c must have one batch size");
+  TORCH_CHECK(batch >= 1 && M >= 1 && N >= 1 && K >= 1, nm,
+              ": empty batch or matrix");
+  TORCH_CHECK(b.size(trans_b ? 2 : 1) == K, nm,
+              ": a and b disagree on K (a is (B,K,M), or (B,M,K) with "
+              "trans_a; b is (B,K,N), or (B,N,K) with trans_b)");
+  TORCH_CHECK(c.size(1) == N && c.size(2) == M, nm,
+              ": c must be (B,N,M) for column-major MxN");
+  TORCH_CHECK(batch <= INT32_MAX && M <= INT32_MAX && N <= INT32_MAX &&
+                  K <= INT32_MAX - 64,
+              nm, ": a size beyond int32");
+  const auto ld = [&](const at::Tensor& t, const char* which) {
+    TORCH_CHECK(t.stride(2) == 1 || t.size(2) == 1, nm, ": ", which,
+                " must have a unit inner stride");
+    if (t.size(1) == 1) return (int)t.size(2);
+    TORCH_CHECK(t.stride(1) >= 1 && t.stride(1) <= INT32_MAX, nm,
+                ": row stride of ", which, " outside 1..2^31-1");
+    return (int)t.stride(1);
+  };
+  ftsgemm::GemmArgs g{};
+  g.M = (int)M, g.N = (int)N, g.K = (int)K, g.batch = (int)batch;
+  g.ragged = true;
+  g.transA = trans_a, g.transB = trans_b;
+  g.lda = ld(a, "a"), g.ldb = ld(b, "b"), g.ldc = ld(c, "c");
+  if (batch > 1)  // a single entry takes the single ragged launch: no strides
+    g.strideA = a.stride(0), g.strideB = b.stride(0), g.strideC = c.stride(0);
+  return g;
+}
+
+// Strided-batched twin of sgemm_ragged: one launch for the whole batch.
+// Fault log as sgemm_batched's, one per entry.
+void sgemm_ragged_batched(int64_t tier, bool abft, bool inject, at::Tensor a,
+                          at::Tensor b, at::Tensor c, double alpha,
+                          double beta, double tau, double inj_mag,
+                          int64_t verify_windows,
+                          c10::optional<at::Tensor> counters,
+                          c10::optional<at::Tensor> events, bool trans_a,
+                          bool trans_b) {
+  launch_gemm("ft_sgemm_ragged_batched", tier,
+              check_ragged_batched_inputs(a, b, c, trans_a, trans_b), abft,
+              inject, a, b, c, alpha, beta, tau, inj_mag, verify_windows,
+              counters, events, /*log_batch=*/c.size(0));
+}
+
+// Floats of segment-checksum scratch a fused sgemm_ragged_batched call on
+// these tensors asks the allocator for: one matrix's worth when a is shared
+// (batch stride 0), `batch` of them otherwise.
+int64_t ragged_batched_workspace_floats(int64_t tier, const at::Tensor& a,
+                                        const at::Tensor& b,
+                                        const at::Tensor& c, bool trans_a,
+                                        bool trans_b) {
+  return (int64_t)ftsgemm::sgemm_abft_workspace_floats(
+      (int)tier, check_ragged_batched_inputs(a, b, c, trans_a, trans_b));
+}
+
 void rocblas_sgemm_nt(at::Tensor a, at::Tensor b, at::Tensor c, double alpha,
                       double beta) {
   int64_t M, N, K;
@@ -442,6 +524,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("trans_a") = false, py::arg("trans_b") = false);
   m.def("ragged_workspace_floats", &ragged_workspace_floats,
         "ABFT scratch floats a fused sgemm_ragged call allocates");
+  m.def("sgemm_ragged_batched", &sgemm_ragged_batched,
+        "strided-batched ragged MFMA SGEMM, one launch per batch",
+        py::arg("tier"), py::arg("abft"), py::arg("inject"), py::arg("a"),
+        py::arg("b"), py::arg("c"), py::arg("alpha"), py::arg("beta"),
+        py::arg("tau"), py::arg("inj_mag"), py::arg("verify_windows"),
+        py::arg("counters") = py::none(), py::arg("events") = py::none(),
+        py::arg("trans_a") = false, py::arg("trans_b") = false);
+  m.def("ragged_batched_workspace_floats", &ragged_batched_workspace_floats,
+        "ABFT scratch floats a fused sgemm_ragged_batched call allocates",
+        py::arg("tier"), py::arg("a"), py::arg("b"), py::arg("c"),
+        py::arg("trans_a") = false, py::arg("trans_b") = false);
   m.def("rocblas_sgemm", &rocblas_sgemm_nt, "rocBLAS oracle SGEMM");
   m.def("baseline_ft", &baseline_ft, "non-fused rocBLAS ABFT baseline",
         py::arg("a"), py::arg("b"), py::arg("c"), py::arg("alpha"),

@@ -102,5 +102,19 @@ lin = ops.FTLinear(515, 777, device="cuda", inject=True, report=report)
 lin(x.requires_grad_()).sum().backward()
 print("linear layer corrected faults:", report.read().corrected)
 
+# 9. batched matrix product: attention scores for 12 heads of dimension 80 on
+#    head views of one (T, heads, 80) projection output.  ft_bmm reads the
+#    (heads, T, 80) views and the transposed keys in place (no copy) and runs
+#    forward and both backward products as one fused-ABFT ragged batched
+#    launch each; one BatchedFaultReport, a slot per head, for all three.
+q = torch.rand((1000, 12, 80), device="cuda", requires_grad=True)
+k = torch.rand((1000, 12, 80), device="cuda", requires_grad=True)
+hreport = ops.BatchedFaultReport(batch=12)
+scores = ops.ft_bmm(q.permute(1, 0, 2), k.permute(1, 0, 2).transpose(1, 2),
+                    inject=True, report=hreport)   # (12, 1000, 1000)
+scores.sum().backward()
+print("per-head corrected faults:", [r.corrected for r in hreport.read()])
+hreport.raise_if_uncorrected()
+
 torch.cuda.synchronize()
 print("examples OK")

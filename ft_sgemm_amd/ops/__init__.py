@@ -267,6 +267,121 @@ def ft_sgemm_ragged(tier: str, a: torch.Tensor, b: torch.Tensor,
                    trans_a=trans_a, trans_b=trans_b)
 
 
+def ragged_batched_layout(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
+                          trans_a: bool = False, trans_b: bool = False):
+    """Validate the operands of a strided-batched ragged call and return
+    (batch, m, n, k, lda, ldb, ldc, sA, sB, sC), leading dimensions and batch
+    strides in floats.  Runs on any device: the CPU-runnable mirror of the
+    launch rules, which the C++ side states once, in gemm_args_error
+    (csrc/dispatch.hip).
+
+    a is (B, K, M), or (B, M, K) with trans_a; b is (B, K, N), or (B, N, K)
+    with trans_b; c is (B, N, M); fp32, any sizes >= 1.  A 2-D a or b is
+    shared by every entry (batch stride 0), exactly like an expand()ed one.
+    Per entry the rules are ragged_layout's: unit inner stride, a row stride
+    of at least the row width, which is the leading dimension.  The batch
+    stride is whatever the tensor has, odd ones included, and no alignment
+    beyond fp32 is asked for.  c's entries must not overlap: they are either
+    disjoint (sC >= (N-1)*ldc + M) or interleaved within a row (sC >= M and
+    (B-1)*sC + M <= ldc), the layout of heads inside a (tokens, heads*dim)
+    tensor.  Raises ValueError."""
+    def err(msg):
+        raise ValueError(f"sgemm_ragged_batched: {msg}")
+
+    if c.dim() != 3:
+        err(f"c must be (B, N, M), got {tuple(c.shape)}")
+    batch, n, m = c.shape
+    for name, x in (("a", a), ("b", b)):
+        if x.dim() not in (2, 3):
+            err(f"{name} must be 2-D or 3-D, got {tuple(x.shape)}")
+        if x.dim() == 3 and x.shape[0] != batch:
+            err(f"batch mismatch: {name} has {x.shape[0]} entries, c {batch}")
+    for name, x in (("a", a), ("b", b), ("c", c)):
+        if x.dtype != torch.float32:
+            err(f"{name} must be float32")
+    ma, k = a.shape[-2:] if trans_a else a.shape[-2:][::-1]
+    nb, kb = b.shape[-2:] if trans_b else b.shape[-2:][::-1]
+    if (ma, nb, kb) != (m, n, k):
+        err(f"a {'(.., M, K)' if trans_a else '(.., K, M)'} = "
+            f"{tuple(a.shape)}, b {'(.., N, K)' if trans_b else '(.., K, N)'} "
+            f"= {tuple(b.shape)} and c (B, N, M) = {tuple(c.shape)} disagree")
+    if min(batch, m, n, k) < 1:
+        err("empty batch or matrix")
+    if batch > MAX_BATCH:
+        err(f"batch {batch} outside 1..{MAX_BATCH}")
+    lds, strides = [], []
+    for name, x in (("a", a), ("b", b), ("c", c)):
+        if x.stride(-1) != 1 and x.shape[-1] != 1:
+            err(f"{name} must have a unit inner stride "
+                f"(strides {tuple(x.stride())})")
+        if x.shape[-2] == 1:
+            lds.append(x.shape[-1])
+        elif x.stride(-2) < x.shape[-1]:
+            err(f"rows of {name} overlap or are broadcast (row stride "
+                f"{x.stride(-2)} < {x.shape[-1]})")
+        else:
+            lds.append(x.stride(-2))
+        strides.append(x.stride(0) if x.dim() == 3 and batch > 1 else 0)
+    lda, ldb, ldc = lds
+    sa, sb, sc = strides
+    if batch > 1:
+        if sc == 0:
+            err("c is broadcast over the batch (batch stride 0)")
+        disjoint = sc >= (n - 1) * ldc + m
+        interleaved = sc >= m and (batch - 1) * sc + m <= ldc
+        if not (disjoint or interleaved):
+            err(f"c entries overlap (batch stride {sc}, row stride {ldc}, "
+                f"N = {n}, M = {m})")
+    return batch, m, n, k, lda, ldb, ldc, sa, sb, sc
+
+
+def _ragged_batched_operands(a, b, c, trans_a, trans_b):
+    """(a, b) as the 3-D views the binding takes, after
+    ragged_batched_layout."""
+    batch = ragged_batched_layout(a, b, c, trans_a, trans_b)[0]
+    return tuple(x if x.dim() == 3 else x.unsqueeze(0).expand(batch, -1, -1)
+                 for x in (a, b))
+
+
+def sgemm_ragged_batched(tier: str, a: torch.Tensor, b: torch.Tensor,
+                         c: torch.Tensor, alpha: float = 1.0,
+                         beta: float = 0.0, *, trans_a: bool = False,
+                         trans_b: bool = False) -> torch.Tensor:
+    """Strided-batched plain SGEMM for any M, N, K >= 1, one launch: for
+    every entry i, c[i] = alpha * A_i B_i^T + beta * c[i] in sgemm_ragged's
+    conventions, trans_a / trans_b included.  Layout rules in
+    ragged_batched_layout; a 2-D a or b is shared by all entries.  c[i] has
+    the bits of sgemm_ragged on the views a[i], b[i], c[i].  In-place on c."""
+    a3, b3 = _ragged_batched_operands(a, b, c, trans_a, trans_b)
+    return _launch("sgemm_ragged_batched", tier, a3, b3, c, alpha, beta,
+                   trans_a=trans_a, trans_b=trans_b)
+
+
+def ft_sgemm_ragged_batched(tier: str, a: torch.Tensor, b: torch.Tensor,
+                            c: torch.Tensor, alpha: float = 1.0,
+                            beta: float = 0.0, inject: bool = True,
+                            tau: float = ERR_BOUND,
+                            inj_mag: float = ERROR_INJECT,
+                            verify_windows: int = 20,
+                            report: BatchedFaultReport | None = None, *,
+                            trans_a: bool = False, trans_b: bool = False
+                            ) -> torch.Tensor:
+    """Strided-batched fused-ABFT SGEMM for any M, N, K >= 1: one
+    checksum-encode launch and one GEMM launch for the whole batch; arguments
+    as ft_sgemm_ragged, layout as sgemm_ragged_batched.  A shared a (2-D or
+    expand()ed) is encoded once.  The injector keeps its per-block rule in
+    every entry, so a victim may lie in an edge tile's padding and is then
+    reported with its padded coordinates.  report: a BatchedFaultReport of
+    the same batch size; entry i logs into slot i."""
+    a3, b3 = _ragged_batched_operands(a, b, c, trans_a, trans_b)
+    if report is not None and report.batch != c.shape[0]:
+        raise ValueError(f"ft_sgemm_ragged_batched: report holds "
+                         f"{report.batch} entries, the batch {c.shape[0]}")
+    return _launch("sgemm_ragged_batched", tier, a3, b3, c, alpha, beta,
+                   (inject, tau, inj_mag, verify_windows), report,
+                   trans_a=trans_a, trans_b=trans_b)
+
+
 def rocblas_sgemm(a, b, c, alpha: float = 1.0, beta: float = 0.0):
     """Kernel id 0: the vendor-BLAS oracle."""
     _require_ext().rocblas_sgemm(a, b, c, alpha, beta)
@@ -437,6 +552,57 @@ RAGGED_THRESHOLDS_NOTE = (
     "not measured")
 
 
+def choose_tier_ragged_batched(m: int, n: int, k: int, batch: int) -> str:
+    """Pick the tier for sgemm_ragged_batched / ft_sgemm_ragged_batched.
+    Every tier fits every shape, so a tier is always returned: choose_tier's
+    batched rule on the grid the ragged launch has, i.e. the single-launch
+    tile-count thresholds applied to ceil tile counts x batch workgroups.
+    batch == 1 gives choose_tier(m, n, k, ragged=True); a shape some tier
+    divides keeps the tier choose_tier(m, n, k, batch) gives its tiled batch.
+    RAGGED_BATCHED_THRESHOLDS_NOTE says what of this is measured."""
+    from .. import kernel_table as kt
+
+    if min(m, n, k, batch) < 1:
+        raise ValueError("choose_tier_ragged_batched: sizes and batch must "
+                         "be >= 1")
+    tiled = choose_tier(m, n, k, batch)
+    if tiled is not None:
+        return tiled
+
+    def tiles(tier):
+        t = kt.TILING[tier]
+        return -(-m // t["bm"]) * -(-n // t["bn"])
+
+    if tiles("huge") * batch >= 384:
+        return "huge"
+    if m >= 4 * n:
+        return "tall"
+    if n >= 4 * m:
+        return "wide"
+    if tiles("large") * batch >= 1024:
+        return "large"
+    return "medium"
+
+
+# How choose_tier_ragged_batched's answers were arrived at.
+RAGGED_BATCHED_THRESHOLDS_NOTE = (
+    "the single-launch tile-count thresholds applied to ceil tile counts x "
+    "batch, with a shape some tier divides keeping the tier of its tiled "
+    "batch.  The thresholds are inherited, not fitted to ragged batched "
+    "runs.  measured (profiles/ragged_batched.txt, MI355X, one batched "
+    "launch, plain and fused no-inject, the chosen tier against huge, large "
+    "and medium), four cells: 1024^3 x16 aligned -> huge, 20-26% ahead of "
+    "large; attention scores 1000x1000x80 x32 NT (32 huge tiles x 32) -> "
+    "huge, which is 5% ahead of large fused and 5% BEHIND it plain; "
+    "attention context 80x1000x1000 x32 NT (skinny, 256 huge tiles) -> wide, "
+    "but medium is 23% (plain) and 35% (fused) FASTER; 1025^3 x16 (45 huge "
+    "tiles x 16, 13 of each 45 edge tiles with one real row or column) -> "
+    "huge, but large is 27% "
+    "(plain) and 21% (fused) FASTER.  The choice is left as specified: two "
+    "losing cells do not support a rule for edge-tile waste or for skinny "
+    "batches.  Every other shape is not measured")
+
+
 def sgemm_auto(a, b, c, alpha: float = 1.0, beta: float = 0.0):
     """Plain SGEMM with automatic tier selection; shapes no hand-written
     tier divides (e.g. M=100) fall back to the rocBLAS vendor path instead
@@ -544,3 +710,4 @@ def torch_reference_batched(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
 
 
 from .linear import FTLinear, ft_linear  # noqa: E402,F401
+from .bmm import ft_bmm  # noqa: E402,F401
