@@ -6,7 +6,12 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <climits>
 #include <cstdint>
+#include <cstring>
+#include <utility>
+#include <vector>
 
 #include "ft_core.h"
 #include "generated/tile_params.h"
@@ -23,7 +28,11 @@ namespace ftsgemm {
   hipError_t launch_tier_ragged_batched_##name(const GemmArgs& g);    \
   hipError_t launch_tier_ragged_batched_tn_##name(const GemmArgs& g); \
   hipError_t launch_tier_ragged_batched_nt_##name(const GemmArgs& g); \
-  hipError_t launch_tier_ragged_batched_tt_##name(const GemmArgs& g);
+  hipError_t launch_tier_ragged_batched_tt_##name(const GemmArgs& g);  \
+  hipError_t launch_tier_ragged_grouped_##name(const GroupedArgs& g);    \
+  hipError_t launch_tier_ragged_grouped_tn_##name(const GroupedArgs& g); \
+  hipError_t launch_tier_ragged_grouped_nt_##name(const GroupedArgs& g); \
+  hipError_t launch_tier_ragged_grouped_tt_##name(const GroupedArgs& g);
 FT_TIER_LIST(FT_DECL)
 #undef FT_DECL
 
@@ -37,7 +46,9 @@ struct TierRow {
   // g.ragged, indexed by transA + 2 * transB: one translation unit each
   hipError_t (*launch_ragged[4])(const GemmArgs&);
   hipError_t (*launch_ragged_batched[4])(const GemmArgs&);  // and batch > 1
+  hipError_t (*launch_ragged_grouped[4])(const GroupedArgs&);
   int bm, bn, bk, wm;
+  int bkf;  // panel depth of the fused twin
 };
 const TierRow kTiers[FT_N_TIERS] = {
 #define FT_ROW(name, BM, BN, BK, WM, WN, MM)                        \
@@ -49,7 +60,11 @@ const TierRow kTiers[FT_N_TIERS] = {
     launch_tier_ragged_batched_tn_##name,                           \
     launch_tier_ragged_batched_nt_##name,                           \
     launch_tier_ragged_batched_tt_##name},                          \
-   BM, BN, BK, WM},
+   {launch_tier_ragged_grouped_##name,                              \
+    launch_tier_ragged_grouped_tn_##name,                           \
+    launch_tier_ragged_grouped_nt_##name,                           \
+    launch_tier_ragged_grouped_tt_##name},                          \
+   BM, BN, BK, WM, FT_TIER_BKF_##name},
     FT_TIER_LIST(FT_ROW)
 #undef FT_ROW
 };
@@ -140,6 +155,124 @@ size_t sgemm_abft_workspace_floats(int tier, const GemmArgs& g) {
   if (!t || g.M < 1 || g.N < 1 || g.K < 1) return 0;
   const size_t nA = g.batch > 1 && g.strideA != 0 ? g.batch : 1;
   return nA * 2 * (size_t)((g.M + t->wm - 1) / t->wm) * abft_sstr(g.K);
+}
+
+// ---- grouped launches (GroupedArgs) ----
+
+namespace {
+
+// Leading dimensions of one grouped problem with 0 resolved to packed.
+struct ResolvedLd {
+  int lda, ldb, ldc;
+};
+ResolvedLd resolve_ld(const GroupedArgs& g, const GroupedProblem& p) {
+  return {p.lda ? p.lda : (g.transA ? p.K : p.M),
+          p.ldb ? p.ldb : (g.transB ? p.K : p.N), p.ldc ? p.ldc : p.M};
+}
+
+bool has_sums(const GroupedProblem& p) {
+  return p.M > 0 && p.N > 0 && p.K > 0;
+}
+
+}  // namespace
+
+const char* grouped_args_error(int tier, const GroupedArgs& g) {
+  const TierRow* t = tier_row(tier);
+  if (!t) return "unknown tier id";
+  if (g.groups < 1 || !g.problems) return "a grouped launch needs entries";
+  long long tiles = 0;
+  std::vector<std::pair<uintptr_t, uintptr_t>> spans;  // C footprints, bytes
+  spans.reserve(g.groups);
+  for (int e = 0; e < g.groups; ++e) {
+    const GroupedProblem& p = g.problems[e];
+    if (p.M < 0 || p.N < 0 || p.K < 0) return "M, N and K must be >= 0";
+    if (p.K > INT_MAX - 64) return "K beyond 2^31 - 65";
+    if (p.M == 0 || p.N == 0) continue;  // nothing read or written
+    // a leading dimension may pad its rows, never cut them; a transposed
+    // operand's rows run along k
+    if ((p.lda && p.lda < (g.transA ? p.K : p.M)) ||
+        (p.ldb && p.ldb < (g.transB ? p.K : p.N)) || (p.ldc && p.ldc < p.M))
+      return "a leading dimension is shorter than its rows";
+    if (!p.C || (p.K > 0 && (!p.A || !p.B)))
+      return "an entry with work needs its A, B and C";
+    if (((uintptr_t)p.A | (uintptr_t)p.B | (uintptr_t)p.C) & 3)
+      return "A, B and C must be 4-byte aligned";
+    tiles += (long long)((p.M + t->bm - 1) / t->bm) *
+             ((p.N + t->bn - 1) / t->bn);
+    if (tiles > INT_MAX) return "more than 2^31 - 1 tiles";
+    const long long ldc = p.ldc ? p.ldc : p.M;
+    const uintptr_t c0 = (uintptr_t)p.C;
+    spans.emplace_back(c0, c0 + 4 * (uintptr_t)((p.N - 1) * ldc + p.M));
+  }
+  // C entries are written: their footprints must be pairwise disjoint.
+  // Sorted by start, each must begin where all before it have ended.
+  std::sort(spans.begin(), spans.end());
+  uintptr_t reach = 0;
+  for (const auto& sp : spans) {
+    if (sp.first < reach)
+      return "C entries overlap as address intervals (entries interleaved "
+             "within a row are not supported by a grouped launch)";
+    reach = std::max(reach, sp.second);
+  }
+  if ((uintptr_t)g.ws & 3) return "ws must be 4-byte aligned";
+  return nullptr;
+}
+
+size_t sgemm_grouped_workspace_floats(int tier, const GroupedArgs& g) {
+  const TierRow* t = tier_row(tier);
+  if (!t || !g.problems) return 0;
+  size_t n = 0;
+  for (int e = 0; e < g.groups; ++e) {
+    const GroupedProblem& p = g.problems[e];
+    if (has_sums(p))
+      n += 2 * (size_t)((p.M + t->wm - 1) / t->wm) * abft_sstr(p.K);
+  }
+  return n;
+}
+
+const char* grouped_table_build(int tier, const GroupedArgs& g,
+                                void* host_table) {
+  if (const char* broken = grouped_args_error(tier, g)) return broken;
+  const TierRow& t = kTiers[tier];
+  std::memset(host_table, 0, grouped_table_bytes(g.groups));
+  int* tile_start = (int*)host_table;
+  GroupedEntry* entry =
+      (GroupedEntry*)((char*)host_table + grouped_prefix_bytes(g.groups));
+  const int bk_used = g.abft ? t.bkf : t.bk;
+  int tiles = 0;
+  long long ws_off = 0;
+  for (int e = 0; e < g.groups; ++e) {
+    const GroupedProblem& p = g.problems[e];
+    const ResolvedLd ld = resolve_ld(g, p);
+    GroupedEntry& d = entry[e];
+    tile_start[e] = tiles;
+    d.A = p.A, d.B = p.B, d.C = p.C;
+    d.M = p.M, d.N = p.N, d.K = p.K;
+    d.lda = ld.lda, d.ldb = ld.ldb, d.ldc = ld.ldc;
+    // the 16-B paths the leading dimensions allow (RaggedFast bits 1, 2, 4);
+    // the kernel clears those the entry's pointers do not (ft_ragged.hpp)
+    d.fast = (ld.lda % 4 == 0 ? 1 : 0) | (ld.ldb % 4 == 0 ? 2 : 0) |
+             (ld.ldc % 4 == 0 ? 4 : 0);
+    d.wstride = window_stride((p.K + bk_used - 1) / bk_used,
+                                      g.abft ? g.verify_windows : 1);
+    d.tiles_x = (p.M + t.bm - 1) / t.bm;
+    tiles += d.tiles_x * ((p.N + t.bn - 1) / t.bn);
+    d.ws_off = ws_off;
+    if (g.abft && has_sums(p)) {
+      d.sstr = abft_sstr(p.K);
+      ws_off += 2LL * ((p.M + t.wm - 1) / t.wm) * d.sstr;
+    }
+  }
+  tile_start[g.groups] = tiles;
+  return nullptr;
+}
+
+hipError_t sgemm_grouped_launch(int tier, const GroupedArgs& g) {
+  if (grouped_args_error(tier, g) || !g.table) return hipErrorInvalidValue;
+  if (g.abft && !g.ws && sgemm_grouped_workspace_floats(tier, g) > 0)
+    return hipErrorInvalidValue;
+  const int tr = (g.transA ? 1 : 0) + (g.transB ? 2 : 0);
+  return kTiers[tier].launch_ragged_grouped[tr](g);
 }
 
 }  // namespace ftsgemm

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "fault_log.h"
+#include "grouped_table.h"
 
 namespace ftsgemm {
 
@@ -93,6 +94,92 @@ inline int abft_sstr(int K) { return (K + 63) & ~63; }
 // (batch > 1, strideA != 0) holds `batch` consecutive copies.  B-side sums
 // are not needed by the ratio-locate scheme.
 size_t sgemm_abft_workspace_floats(int tier, const GemmArgs& g);
+
+// Inject+verify cadence: `steps` K-steps of a tile (classic: K / BK panels,
+// stream-K: 64-k units) in ~`windows` windows of whole steps (reference: 20
+// per GEMM, period K/20, ft_sgemm_huge.cuh:324-327).  Returns steps per
+// window.  Here because the launchers (tier_launch.hpp) and the grouped
+// table (dispatch.hip) must agree on it.
+inline int window_stride(int steps, int windows) {
+  const int stride = steps / (windows > 0 ? windows : 20);
+  return stride < 1 ? 1 : stride;
+}
+
+// One product of a grouped launch, host side: GemmArgs' ragged fields for one
+// entry.  lda / ldb / ldc of 0 mean packed, as there.
+struct GroupedProblem {
+  const float *A, *B;
+  float* C;
+  int M, N, K;
+  int lda, ldb, ldc;
+};
+
+// One grouped launch of the ragged kernels: `groups` products, entry e being
+// C_e = alpha * A_e * B_e^T + beta * C_e with its own sizes, leading
+// dimensions and pointers (problems[e], a host array), in one launch on a
+// one-dimensional grid over the tiles of all entries.  alpha, beta, tau,
+// inj_mag, verify_windows and the transpose flags are common to the launch.
+// There is no limit on groups; the tiles of all entries together must not
+// exceed 2^31 - 1.
+//
+// Unlike a single ragged launch an entry may be empty.  M_e == 0 or N_e == 0:
+// no tiles, no workspace, its log untouched.  K_e == 0 with M_e, N_e > 0:
+// C_e = beta * C_e (exact zeros, C never read, for beta == 0); such an entry
+// reads no operand and no workspace and injects nothing.
+//
+// `table` is device memory of grouped_table_bytes(groups) bytes holding what
+// grouped_table_build wrote for this tier and these arguments (abft,
+// verify_windows, the transpose flags and problems all enter it): the kernels
+// read the entries from it, the launch reads problems only to validate and to
+// size the grids.  `ws` (fused) holds sgemm_grouped_workspace_floats floats;
+// every entry's A is encoded by itself into its own region.  `log` points at
+// the first of `groups` logs laid out like a batch's (GemmArgs): entry e
+// reports into log e.
+struct GroupedArgs {
+  bool abft, inject;
+  float alpha, beta, tau, inj_mag;
+  int verify_windows;  // <= 0: the default of 20
+  bool transA = false, transB = false;
+  int groups = 0;
+  const GroupedProblem* problems = nullptr;  // host, groups of them
+  const void* table = nullptr;               // device
+  float* ws = nullptr;
+  hipStream_t stream = 0;
+  const FaultLog* log = nullptr;
+};
+
+// The rules of a grouped launch, stated once: nullptr when g's problems may
+// be launched on `tier` (g.table and g.ws are not looked at), otherwise a
+// static message naming the rule g breaks.  Per entry
+// they are the single ragged launch's (gemm_args_error) with the empty cases
+// above allowed.  The footprints [C_e, C_e + (N_e-1)*ldc_e + M_e) of the
+// entries that write must be pairwise disjoint as address intervals: entries
+// interleaved within a row of a wider matrix, which a strided batch accepts,
+// are not supported in this form.
+const char* grouped_args_error(int tier, const GroupedArgs& g);
+
+// Fills host_table (grouped_table_bytes(g.groups) bytes of host memory,
+// grouped_table.h) with the table of g on `tier`: tile-start prefix with the
+// total last, and
+// per entry the pointers, sizes, resolved leading dimensions, the fast bits
+// the leading dimensions allow, the window stride
+// window_stride(ceil(K_e / bk_used), verify_windows), sstr and the workspace
+// offset.  g.table and g.ws are not looked at.  The caller copies the table
+// to the device.  Returns grouped_args_error's message, nothing written, when
+// there is one.
+const char* grouped_table_build(int tier, const GroupedArgs& g,
+                                void* host_table);
+
+// Floats of g.ws a fused grouped launch needs: sum_e 2 * ceil(M_e / WM) *
+// abft_sstr(K_e) over the entries with M_e, N_e, K_e > 0, entry e's region
+// laid out like a single launch's (sgemm_abft_workspace_floats) and starting
+// where entry e-1's ends.
+size_t sgemm_grouped_workspace_floats(int tier, const GroupedArgs& g);
+
+// Launch g on tier `tier`: one encode launch (fused) and one GEMM launch.
+// hipErrorInvalidValue, with nothing launched, when grouped_args_error has a
+// message, g.table is missing or a fused launch that needs one has no g.ws.  No allocation, no copy and no sync, so it can be captured.
+hipError_t sgemm_grouped_launch(int tier, const GroupedArgs& g);
 
 // Device self-test of the fused kernels' shared detect / locate / correct
 // (locate_selftest.hip): one single-wave block per case plants up to two

@@ -50,6 +50,27 @@
 // translation units; the batched ones live in
 // kernel_<tier>_ragged_batched_{nn,tn,nt,tt}.hip.
 //
+// Grouped launches (template flag GROUPED, GroupedArgs): a list of products,
+// each with its own M, N, K, leading dimensions and pointers, in one launch.
+// The grid is one-dimensional over the tiles of all entries and the kernel
+// takes a descriptor table (grouped_table.h).  Again only the prologue knows:
+// it finds the block's entry by a binary search of blockIdx.x in the table's
+// tile-start prefix (workgroup-uniform), derives (bx, by) inside the entry
+// with bx fastest, as the two-dimensional grid orders them, and loads the
+// entry's sizes, leading dimensions, pointers, window stride, workspace
+// region and log slot over the kernel arguments of the same names; the fast
+// bits are settled from the entry's own pointers as in a batch.  Below it
+// runs the single-product kernel, so entry e has the bits, fault events
+// included, of the single launch on its operands.  An entry with K == 0 runs
+// no panel: its accumulators stay zero, the epilogue writes beta * C, and the
+// one access that does not depend on the panel loop, the strip prefetch of
+// window 0, is skipped (such an entry has no workspace).  The segment-sum
+// kernels take the entry from a grid dimension sized for the largest entry
+// and leave early where an entry is smaller (docs/ABLATION.md has the
+// alternative).  The GROUPED = false instantiations never look at the table
+// and keep their translation units; the grouped ones live in
+// kernel_<tier>_ragged_grouped_{nn,tn,nt,tt}.hip.
+//
 // Classic decomposition only: no stream-K.
 
 #pragma once
@@ -78,6 +99,40 @@ __device__ __attribute__((always_inline)) inline int ragged_fast_entry(
   if ((uintptr_t)B & 15) fast &= ~RAGGED_FAST_B;
   if ((uintptr_t)C & 15) fast &= ~RAGGED_FAST_C;
   return fast;
+}
+
+// A value every lane of the workgroup holds alike, marked so: what a grouped
+// prologue loads from the table decides workgroup-uniform branches and the
+// LDS side of global_load_lds below.
+__device__ __attribute__((always_inline)) inline int uniform(int v) {
+  return __builtin_amdgcn_readfirstlane(v);
+}
+__device__ __attribute__((always_inline)) inline long long uniform(
+    long long x) {
+  const unsigned long long v = (unsigned long long)x;
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+  return (long long)(((unsigned long long)hi << 32) | lo);
+}
+template <class P>
+__device__ __attribute__((always_inline)) inline P* uniform(P* p) {
+  return (P*)uniform((long long)p);
+}
+
+// The entry that owns tile `tile` of a grouped launch: the last e with
+// tile_start[e] <= tile.  Entries without tiles share their successor's
+// start and are never returned.  tile < tile_start[groups].
+__device__ __attribute__((always_inline)) inline int grouped_entry_of(
+    const GroupTable& gt, int tile) {
+  int lo = 0, hi = gt.groups;  // tile_start[lo] <= tile < tile_start[hi]
+  while (hi - lo > 1) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (gt.tile_start[mid] <= tile)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return uniform(lo);
 }
 
 // Guarded twin of stage_operand: the same ROWS x BK panel into the same LDS
@@ -211,17 +266,13 @@ __device__ __attribute__((always_inline)) inline void segsum_rows4(
 // apart) and its copy of the workspace layout (strideS floats apart).  The
 // sums, their order, the zero fill and the vec test (on the entry's own
 // column) are the unbatched kernel's, which never looks at the strides.
-template <int SEG, bool BATCHED = false>
-__global__ __launch_bounds__(256) void segsum_ragged_kernel(
+// GROUPED: launched on (largest sstr, entries up to 65535); blockIdx.y walks
+// the table's entries in steps of gridDim.y and a block beyond its entry's
+// sstr, or of an entry without workspace, does nothing.
+template <int SEG>
+__device__ __attribute__((always_inline)) inline void segsum_ragged_column(
     int M, int K, int lda, int sstr, const float* __restrict__ A,
-    float* __restrict__ S, long long strideA, long long strideS) {
-  if constexpr (BATCHED) {
-    const long long z = blockIdx.y;
-    A += z * strideA;
-    S += z * strideS;
-  }
-  const int k = blockIdx.x;
-  const int tid = threadIdx.x;
+    float* __restrict__ S, int k, int tid) {
   if (k >= K) {
     const int nbands = (M + SEG - 1) / SEG;
     for (int band = tid; band < nbands; band += 256) {
@@ -257,6 +308,34 @@ __global__ __launch_bounds__(256) void segsum_ragged_kernel(
   }
 }
 
+// Does entry e of a grouped launch have segment sums (a workspace region)?
+__device__ __attribute__((always_inline)) inline bool grouped_has_sums(
+    const GroupedEntry& e) {
+  return e.M > 0 && e.N > 0 && e.K > 0;
+}
+
+template <int SEG, bool BATCHED = false, bool GROUPED = false>
+__global__ __launch_bounds__(256) void segsum_ragged_kernel(
+    int M, int K, int lda, int sstr, const float* __restrict__ A,
+    float* __restrict__ S, long long strideA, long long strideS,
+    GroupTable gt) {
+  if constexpr (GROUPED) {
+    for (int e = blockIdx.y; e < gt.groups; e += gridDim.y) {
+      const GroupedEntry& d = gt.entry[e];
+      if (!grouped_has_sums(d) || (int)blockIdx.x >= d.sstr) continue;
+      segsum_ragged_column<SEG>(d.M, d.K, d.lda, d.sstr, d.A, S + d.ws_off,
+                                blockIdx.x, threadIdx.x);
+    }
+    return;
+  }
+  if constexpr (BATCHED) {
+    const long long z = blockIdx.y;
+    A += z * strideA;
+    S += z * strideS;
+  }
+  segsum_ragged_column<SEG>(M, K, lda, sstr, A, S, blockIdx.x, threadIdx.x);
+}
+
 // Plain and weighted sums of rows [4*g0, 4*(g0+NG)) of one band at one k of a
 // transposed A: the 4-row sums of segsum_rows4 combined by the balanced
 // pairwise tree that segsum_ragged_kernel's xor butterfly forms (lane 0 of a
@@ -286,16 +365,13 @@ __device__ __attribute__((always_inline)) inline void segsum_t_tree(
 // Threads run along k, so the reads are coalesced; blockIdx.x is the band and
 // each thread walks its band's SEG rows.  Rows >= M contribute exact zeros.
 // BATCHED: blockIdx.z picks the matrix and its workspace copy, as above.
-template <int SEG, bool BATCHED = false>
-__global__ __launch_bounds__(256) void segsum_ragged_t_kernel(
+// GROUPED: launched on (most bands, k blocks of the largest sstr, entries up
+// to 65535); blockIdx.z walks the table's entries in steps of gridDim.z, and
+// a block beyond its entry's bands does nothing.
+template <int SEG>
+__device__ __attribute__((always_inline)) inline void segsum_ragged_t_band(
     int M, int K, int lda, int sstr, const float* __restrict__ A,
-    float* __restrict__ S, long long strideA, long long strideS) {
-  if constexpr (BATCHED) {
-    const long long z = blockIdx.z;
-    A += z * strideA;
-    S += z * strideS;
-  }
-  const int band = blockIdx.x;
+    float* __restrict__ S, int band) {
   float* out = S + (size_t)band * 2 * sstr;
   for (int k = blockIdx.y * 256 + threadIdx.x; k < sstr;
        k += gridDim.y * 256) {
@@ -304,6 +380,30 @@ __global__ __launch_bounds__(256) void segsum_ragged_t_kernel(
     out[2 * k] = s;  // ws is only 4-B aligned: no 8-B store
     out[2 * k + 1] = w;
   }
+}
+
+template <int SEG, bool BATCHED = false, bool GROUPED = false>
+__global__ __launch_bounds__(256) void segsum_ragged_t_kernel(
+    int M, int K, int lda, int sstr, const float* __restrict__ A,
+    float* __restrict__ S, long long strideA, long long strideS,
+    GroupTable gt) {
+  if constexpr (GROUPED) {
+    for (int e = blockIdx.z; e < gt.groups; e += gridDim.z) {
+      const GroupedEntry& d = gt.entry[e];
+      if (!grouped_has_sums(d) ||
+          (int)blockIdx.x >= (d.M + SEG - 1) / SEG)
+        continue;
+      segsum_ragged_t_band<SEG>(d.M, d.K, d.lda, d.sstr, d.A, S + d.ws_off,
+                                blockIdx.x);
+    }
+    return;
+  }
+  if constexpr (BATCHED) {
+    const long long z = blockIdx.z;
+    A += z * strideA;
+    S += z * strideS;
+  }
+  segsum_ragged_t_band<SEG>(M, K, lda, sstr, A, S, blockIdx.x);
 }
 
 // The ragged kernel.  Work decomposition, panel body, injector, verify and
@@ -322,9 +422,14 @@ __global__ __launch_bounds__(256) void segsum_ragged_t_kernel(
 //
 // BATCHED: one product per blockIdx.z; the prologue moves the pointers and the
 // fault log to the entry and settles the entry's fast bits (header comment).
+//
+// GROUPED: one tile of some entry per blockIdx.x; the prologue looks the entry
+// up in gt and replaces the sizes, leading dimensions, pointers, window
+// stride, sstr and fast bits by the entry's own (header comment).  verify
+// and inject stride are one value per entry, as the launchers pass them.
 template <int BM, int BN, int BK, int WM, int WN, int MM, bool ABFT,
           bool INJECT, int OCC = 2, bool LOG = false, bool TA = false,
-          bool TB = false, bool BATCHED = false>
+          bool TB = false, bool BATCHED = false, bool GROUPED = false>
 __global__ __launch_bounds__(
     (tile_geom<BM, BN, BK, WM, WN, MM, ABFT>::THREADS),
     OCC) void sgemm_mfma_ragged(int M, int N, int K, int lda, int ldb, int ldc,
@@ -333,8 +438,31 @@ __global__ __launch_bounds__(
                                 float* __restrict__ C, float alpha, float beta,
                                 int verify_iters, int inject_stride, float tau,
                                 float inj_mag, const float* __restrict__ SA,
-                                int sstr, FaultLog flog, BatchStrides bs) {
+                                int sstr, FaultLog flog, BatchStrides bs,
+                                GroupTable gt) {
   using G = tile_geom<BM, BN, BK, WM, WN, MM, ABFT>;
+  int bx = blockIdx.x, by = blockIdx.y;
+  if constexpr (GROUPED) {
+    const int e = grouped_entry_of(gt, blockIdx.x);
+    const GroupedEntry& d = gt.entry[e];
+    const int t = blockIdx.x - uniform(gt.tile_start[e]);
+    const int tiles_x = uniform(d.tiles_x);
+    by = t / tiles_x;
+    bx = t - by * tiles_x;
+    M = uniform(d.M), N = uniform(d.N), K = uniform(d.K);
+    lda = uniform(d.lda), ldb = uniform(d.ldb), ldc = uniform(d.ldc);
+    A = uniform(d.A), B = uniform(d.B), C = uniform(d.C);
+    fast = ragged_fast_entry(uniform(d.fast), A, B, C);
+    verify_iters = inject_stride = uniform(d.wstride);
+    if constexpr (ABFT) {
+      sstr = uniform(d.sstr);
+      SA += uniform(d.ws_off);
+    }
+    if constexpr (LOG) {
+      flog.counters += (long long)e * FLOG_N_COUNTERS;
+      flog.events += (long long)e * flog.capacity * FLOG_EVENT_DWORDS;
+    }
+  }
   if constexpr (BATCHED) {
     const long long z = blockIdx.z;
     A += z * bs.A;
@@ -357,7 +485,6 @@ __global__ __launch_bounds__(
   const thread_pos t = G::thread(threadIdx.x);
   const int tid = t.tid, wave = t.wave, lane = t.lane, sub = t.sub, r = t.r,
             wm_idx = t.wm_idx, wi0 = t.wi0, wj0 = t.wj0;
-  const int bx = blockIdx.x, by = blockIdx.y;
   const int im0 = bx * BM;
   const int jn0 = by * BN;
 
@@ -461,7 +588,10 @@ __global__ __launch_bounds__(
   stage(0, 0);
   stage_mid(0, 0);
   stage_finish(0, 0);
-  if constexpr (ABFT) stage_strip(0, 0);  // window 0 (panels 0..PPS-1)
+  if constexpr (ABFT) {
+    // window 0 (panels 0..PPS-1); a grouped entry with K == 0 has no sums
+    if (!GROUPED || K > 0) stage_strip(0, 0);
+  }
   FT_PARA_SYNC();
   __syncthreads();  // drains in-flight glds
 
@@ -634,11 +764,12 @@ hipError_t launch_tier_ragged(const GemmArgs& g) {
       hipLaunchKernelGGL((segsum_ragged_t_kernel<WM, BATCHED>),
                          dim3(bands, kblocks < 1024 ? kblocks : 1024, nA),
                          dim3(256), 0, g.stream, M, K, lda, cs.sstr, g.A, g.ws,
-                         g.strideA, ws_each);
+                         g.strideA, ws_each, GroupTable{});
     } else {
       hipLaunchKernelGGL((segsum_ragged_kernel<WM, BATCHED>),
                          dim3(cs.sstr, nA), dim3(256), 0, g.stream, M, K, lda,
-                         cs.sstr, g.A, g.ws, g.strideA, ws_each);
+                         cs.sstr, g.A, g.ws, g.strideA, ws_each,
+                         GroupTable{});
     }
   }
   RoctxRange rr_main(
@@ -659,7 +790,68 @@ hipError_t launch_tier_ragged(const GemmArgs& g) {
       });
   hipLaunchKernelGGL(kfn, grid, block, 0, g.stream, M, N, K, lda, ldb, ldc,
                      fast, g.A, g.B, g.C, g.alpha, g.beta, stride, stride,
-                     g.tau, g.inj_mag, cs.SA, cs.sstr, flog, bs);
+                     g.tau, g.inj_mag, cs.SA, cs.sstr, flog, bs, GroupTable{});
+  return hipGetLastError();
+}
+
+// Grouped launch of one tier (instantiated in the _ragged_grouped translation
+// units only): every entry of g.problems on a one-dimensional grid of
+// sum_e ceil(M_e/BM) * ceil(N_e/BN) blocks, one encode launch (fused) and one
+// GEMM launch, both reading the device table g.table that
+// grouped_table_build filled for the same tier and arguments.  The scalar
+// kernel arguments a table entry replaces are passed as zeros.  Checks
+// nothing (sgemm_grouped_launch does); no allocation, no copy and no sync.
+template <int BM, int BN, int BK, int BKF, int WM, int WN, int MM,
+          bool TA = false, bool TB = false>
+hipError_t launch_tier_ragged_grouped(const GroupedArgs& g) {
+  const bool abft = g.abft, inject = g.inject;
+  long long tiles = 0;
+  int max_sstr = 0, max_bands = 0;
+  for (int e = 0; e < g.groups; ++e) {
+    const GroupedProblem& p = g.problems[e];
+    tiles += (long long)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
+    if (p.M > 0 && p.N > 0 && p.K > 0) {
+      const int sstr = abft_sstr(p.K), bands = (p.M + WM - 1) / WM;
+      if (sstr > max_sstr) max_sstr = sstr;
+      if (bands > max_bands) max_bands = bands;
+    }
+  }
+  if (tiles == 0) return hipSuccess;  // every entry is empty
+  const GroupTable gt = grouped_table_view(g.table, g.groups);
+  const int egroups = g.groups < 65535 ? g.groups : 65535;
+  if (abft && max_sstr > 0) {
+    RoctxRange rr("abft_encode_segsum_ragged_grouped");
+    if constexpr (TA) {
+      const int kblocks = (max_sstr + 255) / 256;
+      hipLaunchKernelGGL((segsum_ragged_t_kernel<WM, false, true>),
+                         dim3(max_bands, kblocks < 1024 ? kblocks : 1024,
+                              egroups),
+                         dim3(256), 0, g.stream, 0, 0, 0, 0, nullptr, g.ws, 0LL,
+                         0LL, gt);
+    } else {
+      hipLaunchKernelGGL((segsum_ragged_kernel<WM, false, true>),
+                         dim3(max_sstr, egroups), dim3(256), 0, g.stream, 0, 0,
+                         0, 0, nullptr, g.ws, 0LL, 0LL, gt);
+    }
+  }
+  RoctxRange rr_main(abft ? (inject ? "ft_sgemm_ragged_grouped_abft_inject"
+                                    : "ft_sgemm_ragged_grouped_abft")
+                          : "sgemm_ragged_grouped_plain");
+  const FaultLog flog = attached_log(abft, g.log);
+  const auto kfn = select_variant(
+      abft, inject, flog.counters != nullptr,
+      &sgemm_mfma_ragged<BM, BN, BK, WM, WN, MM, false, false, 2, false, TA,
+                         TB, false, true>,
+      [](auto inj, auto lg) {
+        return &sgemm_mfma_ragged<BM, BN, BKF, WM, WN, MM, true,
+                                  decltype(inj)::value, 2,
+                                  decltype(lg)::value, TA, TB, false, true>;
+      });
+  dim3 block(tile_geom<BM, BN, BK, WM, WN, MM, false>::THREADS);
+  hipLaunchKernelGGL(kfn, dim3((unsigned)tiles), block, 0, g.stream, 0, 0, 0,
+                     0, 0, 0, 0, (const float*)nullptr, (const float*)nullptr,
+                     (float*)nullptr, g.alpha, g.beta, 1, 1, g.tau, g.inj_mag,
+                     (const float*)g.ws, 0, flog, BatchStrides{}, gt);
   return hipGetLastError();
 }
 

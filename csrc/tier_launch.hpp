@@ -63,15 +63,6 @@ void abft_encode(const GemmArgs& g, Checksums& cs) {
                      g.M, g.K, cs.sstr, g.A, g.ws);
 }
 
-// Inject+verify cadence: `steps` K-steps of a tile (classic: K / BK panels,
-// stream-K: 64-k units) in ~`windows` windows of whole steps (reference: 20
-// per GEMM, period K/20, ft_sgemm_huge.cuh:324-327).  Returns steps per
-// window.
-inline int window_stride(int steps, int windows) {
-  const int stride = steps / (windows > 0 ? windows : 20);
-  return stride < 1 ? 1 : stride;
-}
-
 // The fault log a launch runs with: the caller's when one is attached (fused
 // variants only), none otherwise.  Caller-owned: no allocation, no sync, so
 // the launch stays legal under graph capture.

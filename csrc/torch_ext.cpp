@@ -6,6 +6,9 @@
 #include <ATen/cuda/CUDAContext.h>
 #include <torch/extension.h>
 
+#include <algorithm>
+#include <vector>
+
 #include "ft_core.h"
 
 namespace {
@@ -342,6 +345,115 @@ int64_t ragged_batched_workspace_floats(int64_t tier, const at::Tensor& a,
       (int)tier, check_ragged_batched_inputs(a, b, c, trans_a, trans_b));
 }
 
+// One grouped launch, planned: the per-entry problems read off three lists of
+// 2-D tensors (per entry the layout of check_ragged_inputs, with empty sizes
+// allowed), the descriptor table built from them and uploaded once, and the
+// fused launch's workspace.  run() launches on the current stream with no
+// allocation, no copy and no sync.  The plan keeps the tensors alive.
+// ops.grouped_layout is the Python mirror of the rules, which
+// grouped_args_error states.
+class GroupedPlan {
+ public:
+  GroupedPlan(int64_t tier, bool fused, std::vector<at::Tensor> a,
+              std::vector<at::Tensor> b, std::vector<at::Tensor> c,
+              bool trans_a, bool trans_b, int64_t verify_windows)
+      : tier_((int)tier), a_(std::move(a)), b_(std::move(b)),
+        c_(std::move(c)) {
+    const char* nm = "ft_sgemm_grouped";
+    TORCH_CHECK(a_.size() == c_.size() && b_.size() == c_.size(), nm,
+                ": a_list, b_list and c_list must have one length");
+    TORCH_CHECK(!c_.empty() && c_.size() <= (size_t)INT32_MAX, nm,
+                ": empty group");
+    const at::Device dev = c_[0].device();
+    problems_.resize(c_.size());
+    for (size_t e = 0; e < c_.size(); ++e) {
+      const at::Tensor &ta = a_[e], &tb = b_[e], &tc = c_[e];
+      TORCH_CHECK(ta.is_cuda() && ta.device() == dev && tb.device() == dev &&
+                      tc.device() == dev,
+                  nm, ": entry ", e, ": tensors must be on one GPU device");
+      TORCH_CHECK(ta.scalar_type() == at::kFloat &&
+                      tb.scalar_type() == at::kFloat &&
+                      tc.scalar_type() == at::kFloat,
+                  nm, ": entry ", e, ": fp32 only (SGEMM)");
+      TORCH_CHECK(ta.dim() == 2 && tb.dim() == 2 && tc.dim() == 2, nm,
+                  ": entry ", e, ": 2-D tensors expected");
+      const int64_t M = ta.size(trans_a ? 0 : 1), N = tb.size(trans_b ? 0 : 1),
+                    K = ta.size(trans_a ? 1 : 0);
+      TORCH_CHECK(tb.size(trans_b ? 1 : 0) == K && tc.size(0) == N &&
+                      tc.size(1) == M,
+                  nm, ": entry ", e, ": a, b and c disagree on M, N, K");
+      TORCH_CHECK(M <= INT32_MAX && N <= INT32_MAX && K <= INT32_MAX - 64, nm,
+                  ": entry ", e, ": a size beyond int32");
+      // as check_ragged_inputs; an empty tensor is never read or written
+      const auto ld = [&](const at::Tensor& t, const char* which) {
+        if (t.numel() == 0) return (int)std::max<int64_t>(t.size(1), 1);
+        TORCH_CHECK(t.stride(1) == 1 || t.size(1) == 1, nm, ": entry ", e,
+                    ": ", which, " must have a unit inner stride");
+        if (t.size(0) == 1) return (int)t.size(1);
+        TORCH_CHECK(t.stride(0) >= 1 && t.stride(0) <= INT32_MAX, nm,
+                    ": entry ", e, ": row stride of ", which,
+                    " outside 1..2^31-1");
+        return (int)t.stride(0);
+      };
+      ftsgemm::GroupedProblem& p = problems_[e];
+      p.M = (int)M, p.N = (int)N, p.K = (int)K;
+      p.lda = ld(ta, "a"), p.ldb = ld(tb, "b"), p.ldc = ld(tc, "c");
+      p.A = ta.numel() ? ta.const_data_ptr<float>() : nullptr;
+      p.B = tb.numel() ? tb.const_data_ptr<float>() : nullptr;
+      p.C = tc.numel() ? tc.mutable_data_ptr<float>() : nullptr;
+    }
+    g_ = ftsgemm::GroupedArgs{};
+    g_.abft = fused, g_.inject = false;
+    g_.verify_windows = (int)verify_windows;
+    g_.transA = trans_a, g_.transB = trans_b;
+    g_.groups = (int)problems_.size();
+    g_.problems = problems_.data();
+    at::Tensor host = at::empty(
+        {(int64_t)ftsgemm::grouped_table_bytes(g_.groups)},
+        at::TensorOptions().dtype(at::kByte));
+    const char* broken =
+        ftsgemm::grouped_table_build(tier_, g_, host.mutable_data_ptr());
+    TORCH_CHECK(!broken, nm, ": ", broken, " (tier ", tier, ", ", g_.groups,
+                " entries)");
+    table_ = host.to(dev);
+    g_.table = table_.const_data_ptr();
+    const size_t n =
+        fused ? ftsgemm::sgemm_grouped_workspace_floats(tier_, g_) : 0;
+    workspace_ = at::empty({(int64_t)n}, c_[0].options());
+    g_.ws = n ? workspace_.mutable_data_ptr<float>() : nullptr;
+  }
+
+  at::Tensor workspace() const { return workspace_; }
+
+  // counters (groups, 5) / events (groups, capacity, 8): one fault log per
+  // entry (attach_fault_log, batched form).
+  void run(double alpha, double beta, bool inject, double tau, double inj_mag,
+           c10::optional<at::Tensor> counters,
+           c10::optional<at::Tensor> events) {
+    const char* nm = "ft_sgemm_grouped";
+    TORCH_CHECK(g_.abft || !inject, nm, ": inject needs a fused plan");
+    const ftsgemm::FaultLog flog = attach_fault_log(
+        nm, g_.abft, c_[0].device(), counters, events, g_.groups);
+    ftsgemm::GroupedArgs g = g_;
+    g.inject = inject;
+    g.alpha = (float)alpha, g.beta = (float)beta;
+    g.tau = (float)tau, g.inj_mag = (float)inj_mag;
+    g.stream = at::cuda::getCurrentCUDAStream().stream();
+    g.log = flog.counters ? &flog : nullptr;
+    // the rules were held to, with their message, when the plan was built
+    hipError_t err = ftsgemm::sgemm_grouped_launch(tier_, g);
+    TORCH_CHECK(err == hipSuccess, nm,
+                " launch failed: ", hipGetErrorString(err));
+  }
+
+ private:
+  int tier_;
+  std::vector<at::Tensor> a_, b_, c_;
+  std::vector<ftsgemm::GroupedProblem> problems_;
+  ftsgemm::GroupedArgs g_;
+  at::Tensor table_, workspace_;
+};
+
 void rocblas_sgemm_nt(at::Tensor a, at::Tensor b, at::Tensor c, double alpha,
                       double beta) {
   int64_t M, N, K;
@@ -535,6 +647,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "ABFT scratch floats a fused sgemm_ragged_batched call allocates",
         py::arg("tier"), py::arg("a"), py::arg("b"), py::arg("c"),
         py::arg("trans_a") = false, py::arg("trans_b") = false);
+  py::class_<GroupedPlan>(m, "GroupedPlan",
+                          "descriptor table and workspace of a grouped ragged "
+                          "launch, built once")
+      .def(py::init<int64_t, bool, std::vector<at::Tensor>,
+                    std::vector<at::Tensor>, std::vector<at::Tensor>, bool,
+                    bool, int64_t>(),
+           py::arg("tier"), py::arg("fused"), py::arg("a_list"),
+           py::arg("b_list"), py::arg("c_list"), py::arg("trans_a"),
+           py::arg("trans_b"), py::arg("verify_windows"))
+      .def_property_readonly("workspace", &GroupedPlan::workspace)
+      .def("run", &GroupedPlan::run, py::arg("alpha"), py::arg("beta"),
+           py::arg("inject"), py::arg("tau"), py::arg("inj_mag"),
+           py::arg("counters") = py::none(), py::arg("events") = py::none());
   m.def("rocblas_sgemm", &rocblas_sgemm_nt, "rocBLAS oracle SGEMM");
   m.def("baseline_ft", &baseline_ft, "non-fused rocBLAS ABFT baseline",
         py::arg("a"), py::arg("b"), py::arg("c"), py::arg("alpha"),

@@ -116,5 +116,26 @@ scores.sum().backward()
 print("per-head corrected faults:", [r.corrected for r in hreport.read()])
 hreport.raise_if_uncorrected()
 
+# 10. grouped launch: products with their own shapes in ONE launch.  The
+#     expert layer of a mixture-of-experts block is such a group: the rows of
+#     x are sorted by expert, counts (on the host) says how many each expert
+#     owns, one of them none.  Forward, grad_x and grad_weight are one
+#     fused-ABFT grouped launch each; the empty expert gets a zero grad_weight.
+counts = [700, 0, 37, 263]
+xe = torch.rand((sum(counts), 515), device="cuda", requires_grad=True)
+we = torch.rand((4, 777, 515), device="cuda", requires_grad=True)
+ereport = ops.BatchedFaultReport(batch=4)
+ye = ops.ft_grouped_linear(xe, we, counts, inject=True, report=ereport)
+ye.sum().backward()
+print("per-expert corrected faults:", [r.corrected for r in ereport.read()])
+assert not we.grad[1].any()
+#     the launch itself, on any list of (a, b, c): a plan uploads the
+#     descriptor table once, run() launches with no allocation or sync
+ws_, xs_ = list(we.detach().unbind(0)), list(xe.detach().split(counts))
+ys_ = [torch.empty((n, 777), device="cuda") for n in counts]
+plan = ops.GroupedPlan("large", ws_, xs_, ys_, fused=True, trans_a=True,
+                       trans_b=True)
+plan.run(1.0, 0.0)
+
 torch.cuda.synchronize()
 print("examples OK")

@@ -711,3 +711,7 @@ def torch_reference_batched(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
 
 from .linear import FTLinear, ft_linear  # noqa: E402,F401
 from .bmm import ft_bmm  # noqa: E402,F401
+from .grouped import (GROUPED_THRESHOLDS_NOTE, GroupedPlan,  # noqa: E402,F401
+                      choose_tier_grouped, ft_sgemm_grouped, grouped_layout,
+                      sgemm_grouped)
+from .grouped_linear import ft_grouped_linear  # noqa: E402,F401
