@@ -36,6 +36,19 @@ namespace ftsgemm {
 FT_TIER_LIST(FT_DECL)
 #undef FT_DECL
 
+// ragged stream-K twins (kernel_<tier>_ragged_sk_{nn,tn,nt,tt}.hip)
+#define FT_DECL_SK(name)                                         \
+  hipError_t launch_tier_ragged_sk_##name(const GemmArgs& g);    \
+  hipError_t launch_tier_ragged_sk_tn_##name(const GemmArgs& g); \
+  hipError_t launch_tier_ragged_sk_nt_##name(const GemmArgs& g); \
+  hipError_t launch_tier_ragged_sk_tt_##name(const GemmArgs& g); \
+  int ragged_sk_occupancy_##name(const GemmArgs& g);             \
+  int ragged_sk_occupancy_tn_##name(const GemmArgs& g);          \
+  int ragged_sk_occupancy_nt_##name(const GemmArgs& g);          \
+  int ragged_sk_occupancy_tt_##name(const GemmArgs& g);
+FT_STREAMK_TIER_LIST(FT_DECL_SK)
+#undef FT_DECL_SK
+
 namespace {
 
 // One row per tier, in FT_TIER_LIST order: the generator numbers
@@ -73,6 +86,35 @@ const TierRow* tier_row(int tier) {
   return tier >= 0 && tier < FT_N_TIERS ? &kTiers[tier] : nullptr;
 }
 
+// The ragged stream-K twins of a tier, indexed like launch_ragged; null rows
+// for a tier without them (kernel_table.py streamk).
+struct StreamkRow {
+  hipError_t (*launch[4])(const GemmArgs&) = {};
+  int (*occupancy[4])(const GemmArgs&) = {};
+};
+const StreamkRow* streamk_row(int tier) {
+  static const StreamkRow* rows = [] {
+    static StreamkRow r[FT_N_TIERS];
+#define FT_SK_ROW(name)                                                 \
+  r[FT_TIER_ID_##name] = StreamkRow{                                    \
+      {launch_tier_ragged_sk_##name, launch_tier_ragged_sk_tn_##name,   \
+       launch_tier_ragged_sk_nt_##name, launch_tier_ragged_sk_tt_##name}, \
+      {ragged_sk_occupancy_##name, ragged_sk_occupancy_tn_##name,       \
+       ragged_sk_occupancy_nt_##name, ragged_sk_occupancy_tt_##name}};
+    FT_STREAMK_TIER_LIST(FT_SK_ROW)
+#undef FT_SK_ROW
+    return r;
+  }();
+  return tier >= 0 && tier < FT_N_TIERS && rows[tier].launch[0] ? &rows[tier]
+                                                                : nullptr;
+}
+
+// Work units of a ragged stream-K launch: ceil tiles x 64-k windows.
+long long streamk_units(const TierRow& t, const GemmArgs& g) {
+  return (long long)((g.M + t.bm - 1) / t.bm) * ((g.N + t.bn - 1) / t.bn) *
+         ((g.K + 63) / 64);
+}
+
 }  // namespace
 
 // K is tested against the plain kernel's panel depth: every tier's fused
@@ -97,6 +139,16 @@ const char* gemm_args_error(int tier, const GemmArgs& g) {
       (uintptr_t)g.A | (uintptr_t)g.B | (uintptr_t)g.C | (uintptr_t)g.ws;
   if ((g.transA || g.transB) && !g.ragged)
     return "transA / transB need a ragged launch";
+  if (g.sk_grid < 0) return "sk_grid must be >= 0";
+  if (g.sk_grid > 0) {
+    if (!g.ragged || g.batch != 1)
+      return "stream-K (sk_grid > 0) is for a single ragged launch";
+    if (!streamk_row(tier)) return "the tier has no stream-K twin";
+    if (!g.sk_partials || ((uintptr_t)g.sk_partials & 15))
+      return "stream-K needs sk_partials, 16-byte aligned";
+    // the unit index is an int in the kernels
+    if (streamk_units(*t, g) > INT_MAX) return "more than 2^31 - 1 work units";
+  }
   if (g.ragged) {
     if (g.batch < 1 || g.batch > kMaxGridYZ) return "batch outside 1..65535";
     // a leading dimension may pad its rows, never cut them; a transposed
@@ -145,6 +197,7 @@ hipError_t sgemm_tier_launch(int tier, const GemmArgs& g) {
   const TierRow& t = kTiers[tier];
   if (g.ragged) {
     const int tr = (g.transA ? 1 : 0) + (g.transB ? 2 : 0);
+    if (g.sk_grid > 0) return streamk_row(tier)->launch[tr](g);
     return g.batch > 1 ? t.launch_ragged_batched[tr](g) : t.launch_ragged[tr](g);
   }
   return g.batch > 1 ? t.launch_batched(g) : t.launch(g);
@@ -155,6 +208,27 @@ size_t sgemm_abft_workspace_floats(int tier, const GemmArgs& g) {
   if (!t || g.M < 1 || g.N < 1 || g.K < 1) return 0;
   const size_t nA = g.batch > 1 && g.strideA != 0 ? g.batch : 1;
   return nA * 2 * (size_t)((g.M + t->wm - 1) / t->wm) * abft_sstr(g.K);
+}
+
+int sgemm_ragged_streamk_grid(int tier, const GemmArgs& g) {
+  const TierRow* t = tier_row(tier);
+  const StreamkRow* sk = streamk_row(tier);
+  if (!t || !sk || !g.ragged || g.batch != 1 || g.M < 1 || g.N < 1 || g.K < 1)
+    return 0;
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                            dev) != hipSuccess)
+    return 0;
+  const int tr = (g.transA ? 1 : 0) + (g.transB ? 2 : 0);
+  const long long grid = (long long)cus * sk->occupancy[tr](g);
+  return (int)std::min(grid, std::min<long long>(streamk_units(*t, g), INT_MAX));
+}
+
+size_t sgemm_streamk_partials_floats(int tier, int grid) {
+  const TierRow* t = tier_row(tier);
+  if (!t || !streamk_row(tier) || grid < 1) return 0;
+  return (size_t)2 * grid * t->bm * t->bn;
 }
 
 // ---- grouped launches (GroupedArgs) ----

@@ -51,7 +51,19 @@ namespace ftsgemm {
 // ldb >= K.  C, the workspace and its size are unchanged, and the result has
 // the bits of the untransposed launch on the transposed copy.
 //
-// Which shapes, strides, leading dimensions and alignments each of the three
+// sk_grid > 0 (single ragged launches on a tier with a stream-K twin only)
+// runs the ragged stream-K decomposition (ft_ragged_streamk.hpp) on sk_grid
+// workgroups instead of one workgroup per tile: the work is the list of
+// ceil(M/BM) * ceil(N/BN) * ceil(K/64) units (one 64-k window of one tile),
+// cut into sk_grid balanced contiguous ranges; a grid beyond the unit count is
+// clamped to it.  sk_partials is the caller's buffer of
+// sgemm_streamk_partials_floats(tier, sk_grid) floats, 16-byte aligned, that
+// the split tiles are combined through; nothing in it has to be initialised
+// and nothing is kept in it between launches.  The launch allocates nothing,
+// does not sync and reads no environment variable, so it can be captured.
+// sk_grid == 0 is the classic ragged launch.
+//
+// Which shapes, strides, leading dimensions and alignments each of the
 // forms accepts is stated once, in gemm_args_error.
 struct GemmArgs {
   bool abft, inject;
@@ -68,6 +80,8 @@ struct GemmArgs {
   bool ragged = false;
   int lda = 0, ldb = 0, ldc = 0;  // ragged only; 0 = packed
   bool transA = false, transB = false;  // ragged only
+  int sk_grid = 0;                // ragged stream-K workgroups; 0 = classic
+  float* sk_partials = nullptr;   // caller-owned, sk_grid > 0 only
 };
 
 // The launch rules: nullptr when sgemm_tier_launch(tier, g) may launch g,
@@ -94,6 +108,19 @@ inline int abft_sstr(int K) { return (K + 63) & ~63; }
 // (batch > 1, strideA != 0) holds `batch` consecutive copies.  B-side sums
 // are not needed by the ratio-locate scheme.
 size_t sgemm_abft_workspace_floats(int tier, const GemmArgs& g);
+
+// The device grid of a ragged stream-K launch of g on `tier` (g.sk_grid and
+// g.sk_partials are not looked at): CU count x the occupancy of the kernel
+// variant g selects, always the one without a fault log so that attaching a
+// log cannot change the decomposition, clamped to the unit count.  0 for a
+// tier without a stream-K twin or a g that is no single ragged launch.
+// Launches nothing.
+int sgemm_ragged_streamk_grid(int tier, const GemmArgs& g);
+
+// Floats of GemmArgs::sk_partials a stream-K launch on `grid` workgroups
+// needs: two BM x BN slots per workgroup (head and tail partial).  0 for a
+// tier without a stream-K twin or grid < 1.
+size_t sgemm_streamk_partials_floats(int tier, int grid);
 
 // Inject+verify cadence: `steps` K-steps of a tile (classic: K / BK panels,
 // stream-K: 64-k units) in ~`windows` windows of whole steps (reference: 20

@@ -71,7 +71,8 @@
 // and keep their translation units; the grouped ones live in
 // kernel_<tier>_ragged_grouped_{nn,tn,nt,tt}.hip.
 //
-// Classic decomposition only: no stream-K.
+// Classic decomposition only; the stream-K twin of the single launch is
+// ft_ragged_streamk.hpp.
 
 #pragma once
 
@@ -715,6 +716,49 @@ __global__ __launch_bounds__(
     }
 }
 
+// The RaggedFast bits of a launch, decided on the host.  BATCHED: from the
+// leading dimensions alone; the kernel settles them per entry.
+template <bool BATCHED = false>
+int ragged_fast_bits(const GemmArgs& g, int lda, int ldb, int ldc) {
+  const auto fast_ok = [](const void* p, int ld) {
+    return (BATCHED || ((uintptr_t)p & 15) == 0) && ld % 4 == 0;
+  };
+  return (fast_ok(g.A, lda) ? RAGGED_FAST_A : 0) |
+         (fast_ok(g.B, ldb) ? RAGGED_FAST_B : 0) |
+         (fast_ok(g.C, ldc) ? RAGGED_FAST_C : 0);
+}
+
+// The encode of a fused ragged launch (nothing when !g.abft): the segment sums
+// of A, one row per WM-row band, into g.ws (layout at
+// sgemm_abft_workspace_floats).  BATCHED: one copy per entry, or one for all
+// when A is shared; bs.SA becomes the distance between the copies.
+template <int WM, bool TA, bool BATCHED = false>
+void ragged_encode(const GemmArgs& g, int lda, Checksums& cs,
+                   BatchStrides& bs) {
+  if (!g.abft) return;
+  const int M = g.M, K = g.K;
+  cs.sstr = abft_sstr(K);
+  cs.SA = g.ws;
+  const int bands = (M + WM - 1) / WM;
+  const int nA = BATCHED && g.strideA != 0 ? g.batch : 1;
+  // one matrix's rows of the workspace (sgemm_abft_workspace_floats)
+  const long long ws_each = 2LL * bands * cs.sstr;
+  if constexpr (BATCHED) bs.SA = nA == 1 ? 0 : ws_each;
+  RoctxRange rr(BATCHED ? "abft_encode_segsum_ragged_batched"
+                        : "abft_encode_segsum_ragged");
+  if constexpr (TA) {
+    const int kblocks = (cs.sstr + 255) / 256;
+    hipLaunchKernelGGL((segsum_ragged_t_kernel<WM, BATCHED>),
+                       dim3(bands, kblocks < 1024 ? kblocks : 1024, nA),
+                       dim3(256), 0, g.stream, M, K, lda, cs.sstr, g.A, g.ws,
+                       g.strideA, ws_each, GroupTable{});
+  } else {
+    hipLaunchKernelGGL((segsum_ragged_kernel<WM, BATCHED>),
+                       dim3(cs.sstr, nA), dim3(256), 0, g.stream, M, K, lda,
+                       cs.sstr, g.A, g.ws, g.strideA, ws_each, GroupTable{});
+  }
+}
+
 // Ragged launch of one tier: any M, N, K >= 1 on a ceil(M/BM) x ceil(N/BN)
 // grid of sgemm_mfma_ragged.  g.lda / ldb / ldc of 0 mean packed (M, N, M; K
 // for a transposed operand).  TA / TB must equal g.transA / g.transB:
@@ -735,12 +779,7 @@ hipError_t launch_tier_ragged(const GemmArgs& g) {
   const int M = g.M, N = g.N, K = g.K;
   const int lda = g.lda ? g.lda : (TA ? K : M),
             ldb = g.ldb ? g.ldb : (TB ? K : N), ldc = g.ldc ? g.ldc : M;
-  const auto fast_ok = [](const void* p, int ld) {
-    return (BATCHED || ((uintptr_t)p & 15) == 0) && ld % 4 == 0;
-  };
-  const int fast = (fast_ok(g.A, lda) ? RAGGED_FAST_A : 0) |
-                   (fast_ok(g.B, ldb) ? RAGGED_FAST_B : 0) |
-                   (fast_ok(g.C, ldc) ? RAGGED_FAST_C : 0);
+  const int fast = ragged_fast_bits<BATCHED>(g, lda, ldb, ldc);
   const int bk_used = abft ? BKF : BK;
   dim3 grid((M + BM - 1) / BM, (N + BN - 1) / BN, BATCHED ? g.batch : 1);
   dim3 block(tile_geom<BM, BN, BK, WM, WN, MM, false>::THREADS);
@@ -749,29 +788,7 @@ hipError_t launch_tier_ragged(const GemmArgs& g) {
   BatchStrides bs;
   if constexpr (BATCHED) bs = {g.strideA, g.strideB, g.strideC, 0};
   Checksums cs;
-  if (abft) {
-    cs.sstr = abft_sstr(K);
-    cs.SA = g.ws;
-    const int bands = (M + WM - 1) / WM;
-    const int nA = BATCHED && g.strideA != 0 ? g.batch : 1;
-    // one matrix's rows of the workspace (sgemm_abft_workspace_floats)
-    const long long ws_each = 2LL * bands * cs.sstr;
-    if constexpr (BATCHED) bs.SA = nA == 1 ? 0 : ws_each;
-    RoctxRange rr(BATCHED ? "abft_encode_segsum_ragged_batched"
-                          : "abft_encode_segsum_ragged");
-    if constexpr (TA) {
-      const int kblocks = (cs.sstr + 255) / 256;
-      hipLaunchKernelGGL((segsum_ragged_t_kernel<WM, BATCHED>),
-                         dim3(bands, kblocks < 1024 ? kblocks : 1024, nA),
-                         dim3(256), 0, g.stream, M, K, lda, cs.sstr, g.A, g.ws,
-                         g.strideA, ws_each, GroupTable{});
-    } else {
-      hipLaunchKernelGGL((segsum_ragged_kernel<WM, BATCHED>),
-                         dim3(cs.sstr, nA), dim3(256), 0, g.stream, M, K, lda,
-                         cs.sstr, g.A, g.ws, g.strideA, ws_each,
-                         GroupTable{});
-    }
-  }
+  ragged_encode<WM, TA, BATCHED>(g, lda, cs, bs);
   RoctxRange rr_main(
       abft ? (inject ? (BATCHED ? "ft_sgemm_ragged_batched_abft_inject"
                                 : "ft_sgemm_ragged_abft_inject")

@@ -244,16 +244,62 @@ ftsgemm::GemmArgs check_ragged_inputs(const at::Tensor& a, const at::Tensor& b,
 
 // Ragged twin of sgemm: any M, N, K and row-strided operands, either of
 // which may be given transposed.  Fault log as sgemm's.
+// sk_grid > 0: the stream-K decomposition on that many workgroups, combining
+// split tiles through `partials`, a contiguous fp32 tensor on the operands'
+// device of at least streamk_partials_floats(tier, sk_grid) elements
+// (ops.sgemm_ragged allocates it when the caller has none).  What else a
+// stream-K launch asks for is gemm_args_error's to say.
 void sgemm_ragged(int64_t tier, bool abft, bool inject, at::Tensor a,
                   at::Tensor b, at::Tensor c, double alpha, double beta,
                   double tau, double inj_mag, int64_t verify_windows,
                   c10::optional<at::Tensor> counters,
                   c10::optional<at::Tensor> events, bool trans_a,
-                  bool trans_b) {
-  launch_gemm("ft_sgemm_ragged", tier,
-              check_ragged_inputs(a, b, c, trans_a, trans_b), abft, inject, a,
-              b, c, alpha, beta, tau, inj_mag, verify_windows, counters,
-              events, /*log_batch=*/0);
+                  bool trans_b, int64_t sk_grid,
+                  c10::optional<at::Tensor> partials) {
+  const char* nm = "ft_sgemm_ragged";
+  ftsgemm::GemmArgs g = check_ragged_inputs(a, b, c, trans_a, trans_b);
+  TORCH_CHECK(sk_grid >= 0 && sk_grid <= INT32_MAX, nm,
+              ": sk_grid outside 0..2^31-1");
+  TORCH_CHECK(sk_grid > 0 || !partials.has_value(), nm,
+              ": partials go with sk_grid > 0");
+  if (sk_grid > 0) {
+    TORCH_CHECK(partials.has_value(), nm, ": stream-K needs partials");
+    const at::Tensor& p = *partials;
+    TORCH_CHECK(p.device() == a.device() && p.scalar_type() == at::kFloat &&
+                    p.is_contiguous(),
+                nm, ": partials must be a contiguous fp32 tensor on the "
+                "operands' device");
+    const size_t need =
+        ftsgemm::sgemm_streamk_partials_floats((int)tier, (int)sk_grid);
+    TORCH_CHECK(need == 0 || (size_t)p.numel() >= need, nm, ": partials holds ",
+                p.numel(), " floats, a grid of ", sk_grid, " needs ", need);
+    g.sk_grid = (int)sk_grid;
+    g.sk_partials = p.mutable_data_ptr<float>();
+  }
+  launch_gemm(nm, tier, g, abft, inject, a, b, c, alpha, beta, tau, inj_mag,
+              verify_windows, counters, events, /*log_batch=*/0);
+}
+
+// The device grid ops.sgemm_ragged(..., streamk="auto") runs on
+// (sgemm_ragged_streamk_grid); 0 for a tier without a stream-K twin.
+int64_t ragged_streamk_grid(int64_t tier, bool abft, bool inject, int64_t M,
+                            int64_t N, int64_t K, bool trans_a,
+                            bool trans_b) {
+  TORCH_CHECK(M >= 1 && N >= 1 && K >= 1 && M <= INT32_MAX &&
+                  N <= INT32_MAX && K <= INT32_MAX - 64,
+              "ragged_streamk_grid: sizes outside 1..2^31-1");
+  ftsgemm::GemmArgs g{};
+  g.abft = abft, g.inject = inject;
+  g.M = (int)M, g.N = (int)N, g.K = (int)K;
+  g.ragged = true;
+  g.transA = trans_a, g.transB = trans_b;
+  return ftsgemm::sgemm_ragged_streamk_grid((int)tier, g);
+}
+
+int64_t streamk_partials_floats(int64_t tier, int64_t grid) {
+  TORCH_CHECK(grid >= 0 && grid <= INT32_MAX,
+              "streamk_partials_floats: grid outside 0..2^31-1");
+  return (int64_t)ftsgemm::sgemm_streamk_partials_floats((int)tier, (int)grid);
 }
 
 int64_t ragged_workspace_floats(int64_t tier, int64_t M, int64_t N,
@@ -633,9 +679,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("b"), py::arg("c"), py::arg("alpha"), py::arg("beta"),
         py::arg("tau"), py::arg("inj_mag"), py::arg("verify_windows"),
         py::arg("counters") = py::none(), py::arg("events") = py::none(),
-        py::arg("trans_a") = false, py::arg("trans_b") = false);
+        py::arg("trans_a") = false, py::arg("trans_b") = false,
+        py::arg("sk_grid") = 0, py::arg("partials") = py::none());
   m.def("ragged_workspace_floats", &ragged_workspace_floats,
         "ABFT scratch floats a fused sgemm_ragged call allocates");
+  m.def("ragged_streamk_grid", &ragged_streamk_grid,
+        "device grid of a ragged stream-K launch (no launch)",
+        py::arg("tier"), py::arg("abft"), py::arg("inject"), py::arg("m"),
+        py::arg("n"), py::arg("k"), py::arg("trans_a") = false,
+        py::arg("trans_b") = false);
+  m.def("streamk_partials_floats", &streamk_partials_floats,
+        "floats of the partials buffer of a stream-K launch on `grid`",
+        py::arg("tier"), py::arg("grid"));
   m.def("sgemm_ragged_batched", &sgemm_ragged_batched,
         "strided-batched ragged MFMA SGEMM, one launch per batch",
         py::arg("tier"), py::arg("abft"), py::arg("inject"), py::arg("a"),

@@ -18,6 +18,10 @@ from . import golden  # noqa: F401
 from .fault_report import (BatchedFaultReport, FaultCounts,  # noqa: F401
                            FaultEvent, FaultReport, InjectionModel,
                            predict_injected_events, predict_injection_model)
+from .ragged_streamk import (RAGGED_STREAMK_NOTE,  # noqa: F401
+                             ragged_streamk_gate, ragged_streamk_layout,
+                             ragged_streamk_partition,
+                             streamk_partials_floats)
 
 _C = None
 _load_err = None
@@ -227,10 +231,38 @@ def ragged_layout(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
     return (m, n, k, *lds)
 
 
+def _streamk_kw(tier, layout, fused, inject, trans_a, trans_b, streamk,
+                partials, device):
+    """The binding keywords of a ragged call's stream-K arguments: nothing
+    for streamk == 0, otherwise the clamped grid ("auto": the device grid of
+    the kernel variant the call runs) and the partials buffer, allocated on
+    the current stream when the caller has none."""
+    if not isinstance(streamk, str) and streamk == 0:
+        if partials is not None:
+            raise ValueError("sgemm_ragged: partials go with streamk")
+        return {}
+    m, n, k = layout[:3]
+    if streamk == "auto":
+        ragged_streamk_layout(tier, m, n, k, 1)  # the tier has a twin
+        streamk = _require_ext().ragged_streamk_grid(
+            tier_index(tier), fused, inject, m, n, k, trans_a, trans_b)
+        if streamk < 1:
+            raise RuntimeError("sgemm_ragged: the device grid query failed")
+    elif isinstance(streamk, bool) or not isinstance(streamk, int):
+        raise ValueError(f"sgemm_ragged: streamk must be 0, a grid or "
+                         f"'auto', got {streamk!r}")
+    grid = ragged_streamk_layout(tier, m, n, k, streamk, partials)
+    if partials is None:
+        partials = torch.empty(streamk_partials_floats(tier, grid),
+                               dtype=torch.float32, device=device)
+    return dict(sk_grid=grid, partials=partials)
+
+
 def sgemm_ragged(tier: str, a: torch.Tensor, b: torch.Tensor,
                  c: torch.Tensor, alpha: float = 1.0, beta: float = 0.0, *,
-                 trans_a: bool = False, trans_b: bool = False
-                 ) -> torch.Tensor:
+                 trans_a: bool = False, trans_b: bool = False,
+                 streamk: int | str = 0,
+                 partials: torch.Tensor | None = None) -> torch.Tensor:
     """Plain SGEMM for any M, N, K >= 1 and row-strided operands (layout
     rules in ragged_layout), on the ragged twin of `tier`'s classic kernel:
     ceil tile counts, out-of-range operand elements staged as zeros, only the
@@ -241,10 +273,27 @@ def sgemm_ragged(tier: str, a: torch.Tensor, b: torch.Tensor,
     trans_a / trans_b: that operand is given transposed, a as (M, K), b as
     (N, K), and read in place: c = alpha * b @ a^T + beta * c for both, the
     form of a linear layer.  The result has the bits of the untransposed
-    call on x.t().contiguous()."""
-    ragged_layout(a, b, c, trans_a, trans_b)
+    call on x.t().contiguous().
+
+    streamk: 0 is the classic launch, one workgroup per tile.  A positive
+    int runs the stream-K decomposition on that many workgroups (tiers large
+    and huge; a grid beyond the unit count is clamped), "auto" on the device
+    grid, CUs x resident workgroups per CU: the work is cut into balanced
+    ranges of 64-k units (ragged_streamk_partition), so a product with few
+    tiles and a deep K fills the chip, and tiles that several workgroups
+    share are summed in a fixed order by a second kernel.  The result is
+    deterministic but, on a shared tile, not the classic launch's bits: the K
+    sum is cut at other places.  ragged_streamk_gate says where it is
+    expected to pay.
+    partials: the buffer the shared tiles are combined through
+    (ragged_streamk_layout has the rules); None allocates it with
+    torch.empty on the current stream.  Neither form syncs, and with a
+    caller-owned buffer a plain call can be captured in a graph."""
+    layout = ragged_layout(a, b, c, trans_a, trans_b)
     return _launch("sgemm_ragged", tier, a, b, c, alpha, beta,
-                   trans_a=trans_a, trans_b=trans_b)
+                   trans_a=trans_a, trans_b=trans_b,
+                   **_streamk_kw(tier, layout, False, False, trans_a, trans_b,
+                                 streamk, partials, c.device))
 
 
 def ft_sgemm_ragged(tier: str, a: torch.Tensor, b: torch.Tensor,
@@ -252,19 +301,28 @@ def ft_sgemm_ragged(tier: str, a: torch.Tensor, b: torch.Tensor,
                     inject: bool = True, tau: float = ERR_BOUND,
                     inj_mag: float = ERROR_INJECT, verify_windows: int = 20,
                     report: FaultReport | None = None, *,
-                    trans_a: bool = False, trans_b: bool = False
-                    ) -> torch.Tensor:
+                    trans_a: bool = False, trans_b: bool = False,
+                    streamk: int | str = 0,
+                    partials: torch.Tensor | None = None) -> torch.Tensor:
     """Fused-ABFT SGEMM for any M, N, K >= 1 and row-strided operands:
     ft_sgemm's in-kernel verify / locate / correct, injector self-test and
     fault report without a tile fit; arguments as ft_sgemm, layout and
     trans_a / trans_b as sgemm_ragged.  The injector keeps its per-block
     rule, so in an edge tile a victim may lie in the padding: it is corrected
     like any other and reported with its padded coordinates (FaultReport).
-    Transposition moves no fault."""
-    ragged_layout(a, b, c, trans_a, trans_b)
+    Transposition moves no fault.
+
+    streamk / partials: as sgemm_ragged.  Every segment of the stream-K walk
+    is verified and corrected before it leaves the registers; the injector
+    then fires once per (tile, group of verify_windows-derived units) of
+    every segment (predict_injected_events(..., streamk_grid=)), and
+    attaching a report changes neither the grid nor C."""
+    layout = ragged_layout(a, b, c, trans_a, trans_b)
     return _launch("sgemm_ragged", tier, a, b, c, alpha, beta,
                    (inject, tau, inj_mag, verify_windows), report,
-                   trans_a=trans_a, trans_b=trans_b)
+                   trans_a=trans_a, trans_b=trans_b,
+                   **_streamk_kw(tier, layout, True, inject, trans_a, trans_b,
+                                 streamk, partials, c.device))
 
 
 def ragged_batched_layout(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,

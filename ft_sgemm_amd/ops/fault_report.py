@@ -170,7 +170,8 @@ class BatchedFaultReport:
 
 def predict_injected_events(tier: str, m: int, n: int, k: int,
                             verify_windows: int = 20,
-                            ragged: bool = False) -> List[FaultEvent]:
+                            ragged: bool = False,
+                            streamk_grid: int = 0) -> List[FaultEvent]:
     """The exact events the classic fused kernel's injector must produce for
     an (m, n, k) GEMM on `tier`, sorted by (i, j, k_begin).
 
@@ -184,7 +185,20 @@ def predict_injected_events(tier: str, m: int, n: int, k: int,
     every block.  In an edge tile a victim can lie in the padding (i >= m
     or j >= n), and the last window's k_end is a whole number of panels and
     can exceed k: both are predicted as the kernel logs them.
+
+    streamk_grid > 0 (with ragged): model ft_sgemm_ragged(..., streamk=grid)
+    (csrc/ft_ragged_streamk.hpp) instead.  Every segment of
+    ragged_streamk_partition injects once per group of `stride` units counted
+    from its own start, stride = max(1, ceil(k/64) // verify_windows), into
+    acc[0][0][0] of thread ((w_lo + g*stride) * 67 + tile * 13) % THREADS; the
+    group's k range starts at 64 * (w_lo + g*stride) and ends after its last
+    whole panel.
     """
+    if streamk_grid:
+        if not ragged:
+            raise ValueError("streamk_grid needs ragged=True")
+        return _predict_streamk_events(tier, m, n, k, verify_windows,
+                                       streamk_grid)
     t = TILING[tier]
     bm, bn, wm, wn = t["bm"], t["bn"], t["wm"], t["wn"]
     bkf = t.get("bkf", t["bk"])
@@ -211,6 +225,37 @@ def predict_injected_events(tier: str, m: int, n: int, k: int,
                     j=by * bn + (wave % waves_n) * wn + r,
                     k_begin=w * stride * bkf,
                     k_end=min((w + 1) * stride, niter) * bkf,
+                    status=STATUS_CORRECTED, magnitude=ERROR_INJECT,
+                    band_row=bx * bm + (wave // waves_n) * wm,
+                    band_rows=wm))
+    out.sort(key=lambda e: (e.i, e.j, e.k_begin))
+    return out
+
+
+def _predict_streamk_events(tier, m, n, k, verify_windows, grid):
+    from .ragged_streamk import ragged_streamk_partition
+    t = TILING[tier]
+    bm, bn, wm, wn = t["bm"], t["bn"], t["wm"], t["wn"]
+    bkf = t.get("bkf", t["bk"])
+    mm = 16 if t["mfma"] == "f32_16x16x4" else 32
+    nthreads = threads(tier)
+    waves_n = bn // wn
+    upt = -(-k // 64)
+    stride = max(1, upt // (verify_windows if verify_windows > 0 else 20))
+    out = []
+    for segs in ragged_streamk_partition(tier, m, n, k, grid, True)[0]:
+        for tile, bx, by, w_lo, w_hi, _ in segs:
+            kbase = 64 * w_lo
+            npan = -(-(min(k, 64 * w_hi) - kbase) // bkf)
+            for u0 in range(w_lo, w_hi, stride):
+                tid = (u0 * 67 + tile * 13) % nthreads
+                wave, lane = tid >> 6, tid & 63
+                sub, r = lane // mm, lane % mm
+                p_end = min((u0 - w_lo + stride) * (64 // bkf), npan)
+                out.append(FaultEvent(
+                    i=bx * bm + (wave // waves_n) * wm + 4 * sub,
+                    j=by * bn + (wave % waves_n) * wn + r,
+                    k_begin=64 * u0, k_end=kbase + p_end * bkf,
                     status=STATUS_CORRECTED, magnitude=ERROR_INJECT,
                     band_row=bx * bm + (wave // waves_n) * wm,
                     band_rows=wm))

@@ -22,6 +22,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
+from ..kernel_table import TILING
 from .fault_report import FaultReport
 
 
@@ -56,17 +57,28 @@ def _rows(t: torch.Tensor) -> torch.Tensor:
     return t2
 
 
-def _product(a, b, c, beta, trans_a, trans_b, inject, report, tier):
-    from . import choose_tier, ft_sgemm_ragged, ragged_layout
-    m, n, k = ragged_layout(a, b, c, trans_a, trans_b)[:3]
-    ft_sgemm_ragged(tier or choose_tier(m, n, k, ragged=True), a, b, c, 1.0,
-                    beta, inject=inject, report=report, trans_a=trans_a,
-                    trans_b=trans_b)
+def _product(a, b, c, beta, trans_a, trans_b, inject, report, tier,
+             streamk=False):
+    from .. import ops  # the gate is looked up at call time
+    m, n, k = ops.ragged_layout(a, b, c, trans_a, trans_b)[:3]
+    sk = 0
+    if streamk:
+        # the caller's tier, or the first stream-K tier the gate opens: its
+        # True says stream-K there beats the classic launch on the chosen tier
+        for cand in ((tier,) if tier else ("huge", "large")):
+            if TILING[cand].get("streamk", False) and \
+                    ops.ragged_streamk_gate(cand, m, n, k, True):
+                tier, sk = cand, "auto"
+                break
+    tier = tier or ops.choose_tier(m, n, k, ragged=True)
+    ops.ft_sgemm_ragged(tier, a, b, c, 1.0, beta, inject=inject,
+                        report=report, trans_a=trans_a, trans_b=trans_b,
+                        streamk=sk)
 
 
 class _FTLinearFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, inject, report, tier):
+    def forward(ctx, x, weight, bias, inject, report, tier, streamk):
         x2 = _rows(x)
         w = _rows(weight)
         tokens, out = x2.shape[0], w.shape[0]
@@ -75,35 +87,37 @@ class _FTLinearFn(torch.autograd.Function):
         else:
             y = torch.empty((tokens, out), dtype=x.dtype, device=x.device)
         _product(w, x2, y, 0.0 if bias is None else 1.0, True, True, inject,
-                 report, tier)
+                 report, tier, streamk)
         ctx.save_for_backward(x2, w)
         ctx.x_shape = x.shape
         ctx.has_bias = bias is not None
-        ctx.cfg = (inject, report, tier)
+        ctx.cfg = (inject, report, tier, streamk)
         return y.view(*x.shape[:-1], out)
 
     @staticmethod
     def backward(ctx, grad_y):
         x2, w = ctx.saved_tensors
-        inject, report, tier = ctx.cfg
+        inject, report, tier, streamk = ctx.cfg
         g = _rows(grad_y)
         grad_x = grad_w = grad_b = None
         if ctx.needs_input_grad[0]:
             grad_x = torch.empty_like(x2, memory_format=torch.contiguous_format)
-            _product(w, g, grad_x, 0.0, False, True, inject, report, tier)
+            _product(w, g, grad_x, 0.0, False, True, inject, report, tier,
+                     streamk)
             grad_x = grad_x.view(ctx.x_shape)
         if ctx.needs_input_grad[1]:
             grad_w = torch.empty_like(w, memory_format=torch.contiguous_format)
-            _product(x2, g, grad_w, 0.0, False, False, inject, report, tier)
+            _product(x2, g, grad_w, 0.0, False, False, inject, report, tier,
+                     streamk)
         if ctx.has_bias and ctx.needs_input_grad[2]:
             grad_b = g.sum(dim=0)
-        return grad_x, grad_w, grad_b, None, None, None
+        return grad_x, grad_w, grad_b, None, None, None, None
 
 
 def ft_linear(x: torch.Tensor, weight: torch.Tensor,
               bias: torch.Tensor | None = None, *, inject: bool = False,
               report: FaultReport | None = None,
-              tier: str | None = None) -> torch.Tensor:
+              tier: str | None = None, streamk: bool = False) -> torch.Tensor:
     """y = x @ weight^T + bias on the fused-ABFT ragged SGEMM, differentiable.
 
     x (..., in), weight (out, in), bias (out,) or None: fp32 CUDA tensors.
@@ -120,9 +134,15 @@ def ft_linear(x: torch.Tensor, weight: torch.Tensor,
     inject: run the kernels' injector self-test in every product.
     report: one FaultReport that accumulates over all products.
     tier: a tier name for every product; None picks
-    choose_tier(m, n, k, ragged=True) per product."""
+    choose_tier(m, n, k, ragged=True) per product.
+    streamk: let each product take the stream-K decomposition at the device
+    grid where ragged_streamk_gate expects it to win (grad_weight, few tiles
+    and K = tokens, is the case it is for): on `tier` when one is given,
+    otherwise on the first of huge and large the gate opens for the
+    product's shape, in place of the chosen tier.  False, the default, is
+    the classic launch everywhere."""
     _check(x, weight, bias)
-    return _FTLinearFn.apply(x, weight, bias, inject, report, tier)
+    return _FTLinearFn.apply(x, weight, bias, inject, report, tier, streamk)
 
 
 class FTLinear(nn.Linear):
@@ -131,11 +151,14 @@ class FTLinear(nn.Linear):
 
     def __init__(self, in_features: int, out_features: int, bias: bool = True,
                  *, inject: bool = False, report: FaultReport | None = None,
-                 tier: str | None = None, device=None):
+                 tier: str | None = None, streamk: bool = False,
+                 device=None):
         super().__init__(in_features, out_features, bias=bias, device=device,
                          dtype=torch.float32)
         self.inject, self.report, self.tier = inject, report, tier
+        self.streamk = streamk
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return ft_linear(x, self.weight, self.bias, inject=self.inject,
-                         report=self.report, tier=self.tier)
+                         report=self.report, tier=self.tier,
+                         streamk=self.streamk)
