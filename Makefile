@@ -18,7 +18,7 @@ CLI_SRCS := csrc/cli_main.hip csrc/dispatch.hip csrc/rocblas_path.hip \
 CLI_HIPCC = $(HIPCC) -x hip --offload-arch=$(ARCH) -O3 -std=c++17 -Icsrc
 CLI_LIBS := -L$(ROCM)/lib -lrocblas -lroctx64
 
-bin/ft_sgemm: $(CLI_SRCS) csrc/ft_kernels.hpp csrc/ft_streamk.hpp csrc/ft_ragged.hpp csrc/ft_ragged_streamk.hpp csrc/tier_launch.hpp csrc/ft_core.h csrc/fault_log.h csrc/grouped_table.h csrc/generated/tile_params.h
+bin/ft_sgemm: $(CLI_SRCS) csrc/ft_kernels.hpp csrc/ft_streamk.hpp csrc/ft_ragged.hpp csrc/ft_ragged_streamk.hpp csrc/ft_ragged_grouped_streamk.hpp csrc/tier_launch.hpp csrc/ft_core.h csrc/fault_log.h csrc/grouped_table.h csrc/generated/tile_params.h
 	mkdir -p bin
 	$(CLI_HIPCC) $(FTFLAGS) $(CLI_SRCS) $(CLI_LIBS) -o $@
 

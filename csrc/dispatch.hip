@@ -49,6 +49,20 @@ FT_TIER_LIST(FT_DECL)
 FT_STREAMK_TIER_LIST(FT_DECL_SK)
 #undef FT_DECL_SK
 
+// grouped ragged stream-K twins
+// (kernel_<tier>_ragged_gsk_{nn,tn,nt,tt}.hip)
+#define FT_DECL_GSK(name)                                                  \
+  hipError_t launch_tier_ragged_grouped_sk_##name(const GroupedArgs& g);    \
+  hipError_t launch_tier_ragged_grouped_sk_tn_##name(const GroupedArgs& g); \
+  hipError_t launch_tier_ragged_grouped_sk_nt_##name(const GroupedArgs& g); \
+  hipError_t launch_tier_ragged_grouped_sk_tt_##name(const GroupedArgs& g); \
+  int ragged_grouped_sk_occupancy_##name(const GroupedArgs& g);             \
+  int ragged_grouped_sk_occupancy_tn_##name(const GroupedArgs& g);          \
+  int ragged_grouped_sk_occupancy_nt_##name(const GroupedArgs& g);          \
+  int ragged_grouped_sk_occupancy_tt_##name(const GroupedArgs& g);
+FT_STREAMK_TIER_LIST(FT_DECL_GSK)
+#undef FT_DECL_GSK
+
 namespace {
 
 // One row per tier, in FT_TIER_LIST order: the generator numbers
@@ -91,6 +105,8 @@ const TierRow* tier_row(int tier) {
 struct StreamkRow {
   hipError_t (*launch[4])(const GemmArgs&) = {};
   int (*occupancy[4])(const GemmArgs&) = {};
+  hipError_t (*launch_grouped[4])(const GroupedArgs&) = {};
+  int (*occupancy_grouped[4])(const GroupedArgs&) = {};
 };
 const StreamkRow* streamk_row(int tier) {
   static const StreamkRow* rows = [] {
@@ -100,7 +116,15 @@ const StreamkRow* streamk_row(int tier) {
       {launch_tier_ragged_sk_##name, launch_tier_ragged_sk_tn_##name,   \
        launch_tier_ragged_sk_nt_##name, launch_tier_ragged_sk_tt_##name}, \
       {ragged_sk_occupancy_##name, ragged_sk_occupancy_tn_##name,       \
-       ragged_sk_occupancy_nt_##name, ragged_sk_occupancy_tt_##name}};
+       ragged_sk_occupancy_nt_##name, ragged_sk_occupancy_tt_##name},    \
+      {launch_tier_ragged_grouped_sk_##name,                            \
+       launch_tier_ragged_grouped_sk_tn_##name,                         \
+       launch_tier_ragged_grouped_sk_nt_##name,                         \
+       launch_tier_ragged_grouped_sk_tt_##name},                        \
+      {ragged_grouped_sk_occupancy_##name,                              \
+       ragged_grouped_sk_occupancy_tn_##name,                           \
+       ragged_grouped_sk_occupancy_nt_##name,                           \
+       ragged_grouped_sk_occupancy_tt_##name}};
     FT_STREAMK_TIER_LIST(FT_SK_ROW)
 #undef FT_SK_ROW
     return r;
@@ -248,6 +272,24 @@ bool has_sums(const GroupedProblem& p) {
   return p.M > 0 && p.N > 0 && p.K > 0;
 }
 
+// Units per tile of a grouped stream-K entry: 64-k windows, one (empty) for
+// K == 0 (ft_ragged_grouped_streamk.hpp).
+int grouped_upt(const GroupedProblem& p) {
+  return std::max(1, (p.K + 63) / 64);
+}
+
+// Work units of a grouped stream-K launch, summed over the entries with
+// tiles.
+long long grouped_streamk_units(const TierRow& t, const GroupedArgs& g) {
+  long long total = 0;
+  for (int e = 0; e < g.groups; ++e) {
+    const GroupedProblem& p = g.problems[e];
+    total += (long long)((p.M + t.bm - 1) / t.bm) * ((p.N + t.bn - 1) / t.bn) *
+             grouped_upt(p);
+  }
+  return total;
+}
+
 }  // namespace
 
 const char* grouped_args_error(int tier, const GroupedArgs& g) {
@@ -289,6 +331,15 @@ const char* grouped_args_error(int tier, const GroupedArgs& g) {
     reach = std::max(reach, sp.second);
   }
   if ((uintptr_t)g.ws & 3) return "ws must be 4-byte aligned";
+  if (g.sk_grid < 0) return "sk_grid must be >= 0";
+  if (g.sk_grid > 0) {
+    if (!streamk_row(tier)) return "the tier has no stream-K twin";
+    if (!g.sk_partials || ((uintptr_t)g.sk_partials & 15))
+      return "stream-K needs sk_partials, 16-byte aligned";
+    // the unit index is an int in the kernels
+    if (grouped_streamk_units(*t, g) > INT_MAX)
+      return "more than 2^31 - 1 work units";
+  }
   return nullptr;
 }
 
@@ -338,6 +389,24 @@ const char* grouped_table_build(int tier, const GroupedArgs& g,
     }
   }
   tile_start[g.groups] = tiles;
+  if (g.sk_grid > 0) {
+    // the stream-K section, behind the classic table (grouped_table.h)
+    char* sec = (char*)host_table + grouped_sk_section_offset(g.groups);
+    std::memset(sec, 0,
+                grouped_streamk_table_bytes(g.groups) -
+                    grouped_sk_section_offset(g.groups));
+    int* unit_start = (int*)sec;
+    int* istride = (int*)(sec + grouped_prefix_bytes(g.groups));
+    long long units = 0;
+    for (int e = 0; e < g.groups; ++e) {
+      const GroupedProblem& p = g.problems[e];
+      const int upt = grouped_upt(p);
+      unit_start[e] = (int)units;
+      istride[e] = window_stride(upt, g.abft ? g.verify_windows : 1);
+      units += (long long)(tile_start[e + 1] - tile_start[e]) * upt;
+    }
+    unit_start[g.groups] = (int)units;
+  }
   return nullptr;
 }
 
@@ -346,7 +415,37 @@ hipError_t sgemm_grouped_launch(int tier, const GroupedArgs& g) {
   if (g.abft && !g.ws && sgemm_grouped_workspace_floats(tier, g) > 0)
     return hipErrorInvalidValue;
   const int tr = (g.transA ? 1 : 0) + (g.transB ? 2 : 0);
+  if (g.sk_grid > 0) return streamk_row(tier)->launch_grouped[tr](g);
   return kTiers[tier].launch_ragged_grouped[tr](g);
+}
+
+long long sgemm_grouped_streamk_units(int tier, const GroupedArgs& g) {
+  const TierRow* t = tier_row(tier);
+  if (!t || !g.problems || g.groups < 1) return 0;
+  for (int e = 0; e < g.groups; ++e)
+    if (g.problems[e].M < 0 || g.problems[e].N < 0 || g.problems[e].K < 0 ||
+        g.problems[e].K > INT_MAX - 64)
+      return 0;
+  return grouped_streamk_units(*t, g);
+}
+
+int sgemm_grouped_streamk_grid(int tier, const GroupedArgs& g) {
+  const TierRow* t = tier_row(tier);
+  const StreamkRow* sk = streamk_row(tier);
+  if (!t || !sk) return 0;
+  GroupedArgs probe = g;  // the rules without the stream-K ones
+  probe.sk_grid = 0, probe.sk_partials = nullptr;
+  if (grouped_args_error(tier, probe)) return 0;
+  const long long units = grouped_streamk_units(*t, g);
+  if (units < 1) return 0;
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount,
+                            dev) != hipSuccess)
+    return 0;
+  const int tr = (g.transA ? 1 : 0) + (g.transB ? 2 : 0);
+  const long long grid = (long long)cus * sk->occupancy_grouped[tr](g);
+  return (int)std::min(grid, std::min<long long>(units, INT_MAX));
 }
 
 }  // namespace ftsgemm

@@ -162,6 +162,20 @@ struct GroupedProblem {
 // every entry's A is encoded by itself into its own region.  `log` points at
 // the first of `groups` logs laid out like a batch's (GemmArgs): entry e
 // reports into log e.
+//
+// sk_grid > 0 (tiers with a stream-K twin only) runs the grouped stream-K
+// decomposition (ft_ragged_grouped_streamk.hpp) on sk_grid workgroups: the
+// work is the list of units of all entries, entry e having
+// tiles_e * max(1, ceil(K_e / 64)) of them, ordered by entry, tile (bx
+// fastest) and k, cut into sk_grid balanced contiguous ranges; a grid beyond
+// the unit count is clamped to it.  A K_e == 0 entry has one empty unit per
+// tile, whose owner writes beta * C_e.  `table` is then
+// grouped_streamk_table_bytes(groups) bytes, built with the same sk_grid > 0,
+// and sk_partials the caller's buffer of
+// sgemm_streamk_partials_floats(tier, sk_grid) floats, 16-byte aligned.
+// Entry e's fully-owned tiles have the bits of the classic grouped launch;
+// split tiles are summed in a fixed order, so every run gives the same bits.
+// sk_grid == 0 is the classic grouped launch.
 struct GroupedArgs {
   bool abft, inject;
   float alpha, beta, tau, inj_mag;
@@ -173,6 +187,8 @@ struct GroupedArgs {
   float* ws = nullptr;
   hipStream_t stream = 0;
   const FaultLog* log = nullptr;
+  int sk_grid = 0;               // grouped stream-K workgroups; 0 = classic
+  float* sk_partials = nullptr;  // caller-owned, sk_grid > 0 only
 };
 
 // The rules of a grouped launch, stated once: nullptr when g's problems may
@@ -191,7 +207,11 @@ const char* grouped_args_error(int tier, const GroupedArgs& g);
 // per entry the pointers, sizes, resolved leading dimensions, the fast bits
 // the leading dimensions allow, the window stride
 // window_stride(ceil(K_e / bk_used), verify_windows), sstr and the workspace
-// offset.  g.table and g.ws are not looked at.  The caller copies the table
+// offset.  With g.sk_grid > 0 host_table is
+// grouped_streamk_table_bytes(g.groups) bytes and the stream-K section
+// (unit-start prefix, per-entry verify stride in units) is filled behind
+// the classic table, which is the same bytes either way.  g.table and g.ws
+// are not looked at.  The caller copies the table
 // to the device.  Returns grouped_args_error's message, nothing written, when
 // there is one.
 const char* grouped_table_build(int tier, const GroupedArgs& g,
@@ -206,7 +226,22 @@ size_t sgemm_grouped_workspace_floats(int tier, const GroupedArgs& g);
 // Launch g on tier `tier`: one encode launch (fused) and one GEMM launch.
 // hipErrorInvalidValue, with nothing launched, when grouped_args_error has a
 // message, g.table is missing or a fused launch that needs one has no g.ws.  No allocation, no copy and no sync, so it can be captured.
+// g.sk_grid > 0: the encode, the grouped stream-K kernel and the fixup pass.
 hipError_t sgemm_grouped_launch(int tier, const GroupedArgs& g);
+
+// The device grid of a grouped stream-K launch of g on `tier` (g.sk_grid,
+// g.sk_partials and g.table are not looked at): CU count x the occupancy of
+// the kernel variant g selects, always the one without a fault log, clamped
+// to the unit count.  0 for a tier without a stream-K twin, a g that breaks a
+// rule or one without units.  Launches nothing.
+int sgemm_grouped_streamk_grid(int tier, const GroupedArgs& g);
+
+// Work units of a grouped stream-K launch of g on `tier`: sum over the
+// entries of ceil(M_e/BM) * ceil(N_e/BN) * max(1, ceil(K_e/64)).  A launch
+// runs on min(sk_grid, units) workgroups and needs
+// sgemm_streamk_partials_floats(tier, that) floats of partials.  0 for an
+// unknown tier or sizes outside grouped_args_error's range.
+long long sgemm_grouped_streamk_units(int tier, const GroupedArgs& g);
 
 // Device self-test of the fused kernels' shared detect / locate / correct
 // (locate_selftest.hip): one single-wave block per case plants up to two

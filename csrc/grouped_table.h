@@ -9,7 +9,8 @@
 //   GroupedEntry entry[groups]
 //
 // An entry with M == 0 or N == 0 has no tiles: its tile_start equals its
-// successor's and no block ever loads its descriptor.
+// successor's and no block ever loads its descriptor.  A stream-K launch
+// appends one more section (GroupSkTable, below).
 #pragma once
 
 #include <cstddef>
@@ -54,6 +55,39 @@ inline GroupTable grouped_table_view(const void* table, int groups) {
   const char* p = (const char*)table;
   return {(const int*)p, (const GroupedEntry*)(p + grouped_prefix_bytes(groups)),
           groups};
+}
+
+// The stream-K section of a table (ft_ragged_grouped_streamk.hpp), appended
+// behind the entries so that what the classic grouped kernels read keeps its
+// place and meaning.  A table built with GroupedArgs::sk_grid > 0 is
+// grouped_streamk_table_bytes(groups) bytes long:
+//
+//   (the classic table, padded to 16 bytes)
+//   int unit_start[groups + 1]   exclusive prefix of the entries' work units
+//                                tiles_e * max(1, ceil(K_e / 64)); the last
+//                                is the launch's unit count
+//   (padding to 16 bytes)
+//   int istride[groups]          verify / inject stride of entry e in 64-k
+//                                units: window_stride(upt_e, verify_windows)
+struct GroupSkTable {
+  const int* unit_start = nullptr;
+  const int* istride = nullptr;
+};
+
+inline size_t grouped_sk_section_offset(int groups) {
+  return (grouped_table_bytes(groups) + 15) & ~(size_t)15;
+}
+
+inline size_t grouped_streamk_table_bytes(int groups) {
+  return groups < 0 ? 0
+                    : grouped_sk_section_offset(groups) +
+                          grouped_prefix_bytes(groups) +
+                          (size_t)groups * sizeof(int);
+}
+
+inline GroupSkTable grouped_sk_table_view(const void* table, int groups) {
+  const char* p = (const char*)table + grouped_sk_section_offset(groups);
+  return {(const int*)p, (const int*)(p + grouped_prefix_bytes(groups))};
 }
 
 }  // namespace ftsgemm

@@ -398,11 +398,20 @@ int64_t ragged_batched_workspace_floats(int64_t tier, const at::Tensor& a,
 // allocation, no copy and no sync.  The plan keeps the tensors alive.
 // ops.grouped_layout is the Python mirror of the rules, which
 // grouped_args_error states.
+//
+// sk_grid: 0 plans the classic launch, G > 0 the grouped stream-K launch on
+// G workgroups, -1 on the device grid (sgemm_grouped_streamk_grid).  The grid
+// is clamped to the unit count and fixed for the plan, since the partials
+// buffer is sized by it: `partials` (contiguous fp32 on the operands' device,
+// 16-byte aligned, at least streamk_partials_floats(tier, clamped grid)
+// elements) or, when none is given, a buffer the plan allocates here.  A
+// group without units plans the classic launch, which launches nothing.
 class GroupedPlan {
  public:
   GroupedPlan(int64_t tier, bool fused, std::vector<at::Tensor> a,
               std::vector<at::Tensor> b, std::vector<at::Tensor> c,
-              bool trans_a, bool trans_b, int64_t verify_windows)
+              bool trans_a, bool trans_b, int64_t verify_windows,
+              int64_t sk_grid, c10::optional<at::Tensor> partials)
       : tier_((int)tier), a_(std::move(a)), b_(std::move(b)),
         c_(std::move(c)) {
     const char* nm = "ft_sgemm_grouped";
@@ -454,8 +463,43 @@ class GroupedPlan {
     g_.transA = trans_a, g_.transB = trans_b;
     g_.groups = (int)problems_.size();
     g_.problems = problems_.data();
+    TORCH_CHECK(sk_grid >= -1 && sk_grid <= INT32_MAX, nm,
+                ": sk_grid outside -1..2^31-1");
+    TORCH_CHECK(sk_grid != 0 || !partials.has_value(), nm,
+                ": partials go with sk_grid != 0");
+    if (sk_grid != 0) {
+      TORCH_CHECK(ftsgemm::sgemm_streamk_partials_floats(tier_, 1) > 0, nm,
+                  ": the tier has no stream-K twin (tier ", tier, ")");
+      const long long units =
+          ftsgemm::sgemm_grouped_streamk_units(tier_, g_);
+      TORCH_CHECK(units <= INT32_MAX, nm, ": more than 2^31 - 1 work units");
+      if (sk_grid < 0) sk_grid = ftsgemm::sgemm_grouped_streamk_grid(tier_, g_);
+      TORCH_CHECK(units == 0 || sk_grid > 0, nm,
+                  ": no device grid for the grouped stream-K launch");
+      sk_grid = std::min<int64_t>(sk_grid, units);
+    }
+    if (sk_grid > 0) {
+      const size_t need =
+          ftsgemm::sgemm_streamk_partials_floats(tier_, (int)sk_grid);
+      if (partials.has_value()) {
+        const at::Tensor& p = *partials;
+        TORCH_CHECK(p.device() == dev && p.scalar_type() == at::kFloat &&
+                        p.is_contiguous(),
+                    nm, ": partials must be a contiguous fp32 tensor on the "
+                    "operands' device");
+        TORCH_CHECK((size_t)p.numel() >= need, nm, ": partials holds ",
+                    p.numel(), " floats, a grid of ", sk_grid, " needs ", need);
+        partials_ = p;
+      } else {
+        partials_ = at::empty({(int64_t)need}, c_[0].options());
+      }
+      g_.sk_grid = (int)sk_grid;
+      g_.sk_partials = partials_.mutable_data_ptr<float>();
+    }
     at::Tensor host = at::empty(
-        {(int64_t)ftsgemm::grouped_table_bytes(g_.groups)},
+        {(int64_t)(g_.sk_grid > 0
+                       ? ftsgemm::grouped_streamk_table_bytes(g_.groups)
+                       : ftsgemm::grouped_table_bytes(g_.groups))},
         at::TensorOptions().dtype(at::kByte));
     const char* broken =
         ftsgemm::grouped_table_build(tier_, g_, host.mutable_data_ptr());
@@ -470,6 +514,12 @@ class GroupedPlan {
   }
 
   at::Tensor workspace() const { return workspace_; }
+  // the clamped stream-K grid (0: classic) and its partials buffer
+  int64_t streamk_grid() const { return g_.sk_grid; }
+  c10::optional<at::Tensor> partials() const {
+    return g_.sk_grid > 0 ? c10::optional<at::Tensor>(partials_)
+                          : c10::nullopt;
+  }
 
   // counters (groups, 5) / events (groups, capacity, 8): one fault log per
   // entry (attach_fault_log, batched form).
@@ -497,7 +547,7 @@ class GroupedPlan {
   std::vector<at::Tensor> a_, b_, c_;
   std::vector<ftsgemm::GroupedProblem> problems_;
   ftsgemm::GroupedArgs g_;
-  at::Tensor table_, workspace_;
+  at::Tensor table_, workspace_, partials_;
 };
 
 void rocblas_sgemm_nt(at::Tensor a, at::Tensor b, at::Tensor c, double alpha,
@@ -707,11 +757,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
                           "launch, built once")
       .def(py::init<int64_t, bool, std::vector<at::Tensor>,
                     std::vector<at::Tensor>, std::vector<at::Tensor>, bool,
-                    bool, int64_t>(),
+                    bool, int64_t, int64_t, c10::optional<at::Tensor>>(),
            py::arg("tier"), py::arg("fused"), py::arg("a_list"),
            py::arg("b_list"), py::arg("c_list"), py::arg("trans_a"),
-           py::arg("trans_b"), py::arg("verify_windows"))
+           py::arg("trans_b"), py::arg("verify_windows"),
+           py::arg("sk_grid") = 0, py::arg("partials") = py::none())
       .def_property_readonly("workspace", &GroupedPlan::workspace)
+      .def_property_readonly("streamk_grid", &GroupedPlan::streamk_grid)
+      .def_property_readonly("partials", &GroupedPlan::partials)
       .def("run", &GroupedPlan::run, py::arg("alpha"), py::arg("beta"),
            py::arg("inject"), py::arg("tau"), py::arg("inj_mag"),
            py::arg("counters") = py::none(), py::arg("events") = py::none());

@@ -17,7 +17,13 @@ from ..kernel_table import (ERR_BOUND, ERROR_INJECT, KERNEL_TABLE, TIERS)
 from . import golden  # noqa: F401
 from .fault_report import (BatchedFaultReport, FaultCounts,  # noqa: F401
                            FaultEvent, FaultReport, InjectionModel,
-                           predict_injected_events, predict_injection_model)
+                           predict_injected_events,
+                           predict_injected_events_grouped,
+                           predict_injection_model)
+from .grouped_streamk import (GROUPED_STREAMK_NOTE,  # noqa: F401
+                              grouped_streamk_gate, grouped_streamk_layout,
+                              grouped_streamk_partition,
+                              grouped_streamk_units)
 from .ragged_streamk import (RAGGED_STREAMK_NOTE,  # noqa: F401
                              ragged_streamk_gate, ragged_streamk_layout,
                              ragged_streamk_partition,

@@ -263,6 +263,63 @@ def _predict_streamk_events(tier, m, n, k, verify_windows, grid):
     return out
 
 
+def predict_injected_events_grouped(tier: str, shapes,
+                                    verify_windows: int = 20,
+                                    streamk_grid: int = 0
+                                    ) -> List[List[FaultEvent]]:
+    """Per entry of a grouped fused launch on `tier`, the exact events its
+    injector must produce, each list sorted by (i, j, k_begin).  shapes:
+    (m, n, k, ...) per entry, as grouped_layout returns them.
+
+    streamk_grid == 0 models ft_sgemm_grouped's classic launch: entry e has
+    the events of ft_sgemm_ragged on its own shape, an empty entry none.
+
+    streamk_grid > 0 models ft_sgemm_grouped(..., streamk=grid)
+    (csrc/ft_ragged_grouped_streamk.hpp).  Every segment of
+    grouped_streamk_partition injects once per group of stride_e units
+    counted from its own start, stride_e = max(1, upt_e // verify_windows),
+    into acc[0][0][0] of thread ((w_lo + g*stride_e) * 67 + tile * 13) %
+    THREADS with `tile` the entry-local tile index; a segment of a k == 0
+    entry has no panels and injects nothing.  Coordinates are the entry's
+    own."""
+    if not streamk_grid:
+        return [predict_injected_events(tier, s[0], s[1], s[2],
+                                        verify_windows, ragged=True)
+                if min(s[:3]) > 0 else [] for s in shapes]
+    from .grouped_streamk import grouped_streamk_partition
+    t = TILING[tier]
+    bm, bn, wm, wn = t["bm"], t["bn"], t["wm"], t["wn"]
+    bkf = t.get("bkf", t["bk"])
+    mm = 16 if t["mfma"] == "f32_16x16x4" else 32
+    nthreads = threads(tier)
+    waves_n = bn // wn
+    windows = verify_windows if verify_windows > 0 else 20
+    out = [[] for _ in shapes]
+    for segs in grouped_streamk_partition(tier, shapes, streamk_grid)[0]:
+        for e, tile, bx, by, w_lo, w_hi, _ in segs:
+            k = shapes[e][2]
+            if k == 0:
+                continue
+            stride = max(1, -(-k // 64) // windows)
+            kbase = 64 * w_lo
+            npan = -(-(min(k, 64 * w_hi) - kbase) // bkf)
+            for u0 in range(w_lo, w_hi, stride):
+                tid = (u0 * 67 + tile * 13) % nthreads
+                wave, lane = tid >> 6, tid & 63
+                sub, r = lane // mm, lane % mm
+                p_end = min((u0 - w_lo + stride) * (64 // bkf), npan)
+                out[e].append(FaultEvent(
+                    i=bx * bm + (wave // waves_n) * wm + 4 * sub,
+                    j=by * bn + (wave % waves_n) * wn + r,
+                    k_begin=64 * u0, k_end=kbase + p_end * bkf,
+                    status=STATUS_CORRECTED, magnitude=ERROR_INJECT,
+                    band_row=bx * bm + (wave // waves_n) * wm,
+                    band_rows=wm))
+    for ev in out:
+        ev.sort(key=lambda x: (x.i, x.j, x.k_begin))
+    return out
+
+
 class InjectionModel(NamedTuple):
     """What the classic fused kernel must do with its injector's faults for
     a given (tau, inj_mag); see predict_injection_model."""

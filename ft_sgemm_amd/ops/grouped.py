@@ -155,24 +155,66 @@ class GroupedPlan:
     fused: plan the fused-ABFT twin; the table's verify windows depend on it
     and on verify_windows, so a plan is one or the other.
     workspace: the fused launch's segment-checksum scratch (empty for a plain
-    plan); every run() rewrites all of it that is read."""
+    plan); every run() rewrites all of it that is read.
+
+    streamk: 0 (the default) plans the classic launch, one workgroup per
+    output tile.  G >= 1 plans the grouped stream-K launch
+    (csrc/ft_ragged_grouped_streamk.hpp) on G workgroups, "auto" on the
+    device grid (CUs x resident workgroups of the kernel the plan selects):
+    the 64-k units of all entries, K == 0 entries counting one empty unit
+    per tile, are cut into balanced contiguous ranges, so a deep entry is
+    shared by many workgroups and a shallow one costs little.  Tiers large
+    and huge only.  The grid is clamped to the unit count and fixed for the
+    plan (streamk_grid reports it; 0 for a classic plan or a group without
+    units), since the partials buffer is sized by it.
+    partials: the buffer split tiles are combined through, a contiguous
+    16-byte aligned fp32 tensor of at least
+    streamk_partials_floats(tier, streamk_grid) elements on the operands'
+    device; None lets the plan allocate it once, here.  Nothing in it has to
+    be initialised and nothing is kept in it between runs.  Tiles one
+    workgroup owns whole have the classic launch's bits; split tiles are
+    summed in a fixed order, so every run gives the same bits."""
 
     def __init__(self, tier: str, a_list, b_list, c_list, *,
                  fused: bool = False, trans_a: bool = False,
-                 trans_b: bool = False, verify_windows: int = 20):
+                 trans_b: bool = False, verify_windows: int = 20,
+                 streamk=0, partials: torch.Tensor | None = None):
         from . import _require_ext, tier_index
+        from .grouped_streamk import grouped_streamk_layout
         a_list, b_list, c_list = list(a_list), list(b_list), list(c_list)
         self.shapes = grouped_layout(a_list, b_list, c_list, trans_a, trans_b)
         self.tier, self.fused = tier, bool(fused)
         self.groups = len(c_list)
+        if streamk == "auto":
+            sk_grid = -1
+            grouped_streamk_layout(tier, self.shapes, 1)
+        elif isinstance(streamk, bool) or not isinstance(streamk, int) \
+                or streamk < 0:
+            raise ValueError(f"GroupedPlan: streamk must be 0, a grid >= 1 "
+                             f"or 'auto', got {streamk!r}")
+        else:
+            sk_grid = streamk
+            if sk_grid:
+                grouped_streamk_layout(tier, self.shapes, sk_grid, partials)
+        if not sk_grid and partials is not None:
+            raise ValueError("GroupedPlan: partials go with streamk")
         self._impl = _require_ext().GroupedPlan(
             tier_index(tier), self.fused, a_list, b_list, c_list,
-            bool(trans_a), bool(trans_b), int(verify_windows))
+            bool(trans_a), bool(trans_b), int(verify_windows), sk_grid,
+            partials)
         self._c = c_list
 
     @property
     def workspace(self) -> torch.Tensor:
         return self._impl.workspace
+
+    @property
+    def streamk_grid(self) -> int:
+        return self._impl.streamk_grid
+
+    @property
+    def partials(self) -> torch.Tensor | None:
+        return self._impl.partials
 
     def run(self, alpha: float = 1.0, beta: float = 0.0, *,
             inject: bool = False, tau: float = ERR_BOUND,
@@ -194,7 +236,8 @@ class GroupedPlan:
 
 def sgemm_grouped(tier: str, a_list, b_list, c_list, alpha: float = 1.0,
                   beta: float = 0.0, *, trans_a: bool = False,
-                  trans_b: bool = False):
+                  trans_b: bool = False, streamk=0,
+                  partials: torch.Tensor | None = None):
     """Grouped plain SGEMM, one launch: for every entry e,
     c_list[e] = alpha * A_e B_e^T + beta * c_list[e] in sgemm_ragged's
     conventions, each entry with its own sizes, leading dimensions and
@@ -202,9 +245,12 @@ def sgemm_grouped(tier: str, a_list, b_list, c_list, alpha: float = 1.0,
     flags are common to the launch.  c_list[e] has the bits of sgemm_ragged
     on (a_list[e], b_list[e], c_list[e]); an entry with K == 0 becomes
     beta * c (exact zeros for beta == 0, c not read).  In place on the c
-    tensors, which are returned.  Builds a GroupedPlan and runs it once."""
+    tensors, which are returned.  Builds a GroupedPlan and runs it once.
+    streamk, partials: the grouped stream-K launch, as GroupedPlan's; split
+    tiles then differ from sgemm_ragged in summation order only."""
     return GroupedPlan(tier, a_list, b_list, c_list, fused=False,
-                       trans_a=trans_a, trans_b=trans_b).run(alpha, beta)
+                       trans_a=trans_a, trans_b=trans_b, streamk=streamk,
+                       partials=partials).run(alpha, beta)
 
 
 def ft_sgemm_grouped(tier: str, a_list, b_list, c_list, alpha: float = 1.0,
@@ -212,16 +258,21 @@ def ft_sgemm_grouped(tier: str, a_list, b_list, c_list, alpha: float = 1.0,
                      tau: float = ERR_BOUND, inj_mag: float = ERROR_INJECT,
                      verify_windows: int = 20,
                      report: BatchedFaultReport | None = None, *,
-                     trans_a: bool = False, trans_b: bool = False):
+                     trans_a: bool = False, trans_b: bool = False,
+                     streamk=0, partials: torch.Tensor | None = None):
     """Grouped fused-ABFT SGEMM: one checksum-encode launch and one GEMM
     launch for all entries; arguments as ft_sgemm_ragged, operands as
     sgemm_grouped.  Every entry's A is encoded by itself into its own region
     of one workspace.  Entry e has the bits, and reports the events, of
     ft_sgemm_ragged on its own operands; an entry with K == 0 injects
     nothing.  report: a BatchedFaultReport of len(c_list) entries; entry e
-    logs into slot e, an entry without tiles leaves its slot untouched."""
+    logs into slot e, an entry without tiles leaves its slot untouched.
+    streamk, partials: the grouped stream-K launch, as GroupedPlan's; the
+    events are then those of
+    fault_report.predict_injected_events_grouped(..., streamk_grid=grid)."""
     return GroupedPlan(tier, a_list, b_list, c_list, fused=True,
                        trans_a=trans_a, trans_b=trans_b,
-                       verify_windows=verify_windows).run(
+                       verify_windows=verify_windows, streamk=streamk,
+                       partials=partials).run(
                            alpha, beta, inject=inject, tau=tau,
                            inj_mag=inj_mag, report=report)

@@ -94,18 +94,27 @@ def _split(t: torch.Tensor, counts):
 
 
 def _product(a_list, b_list, c_list, beta, trans_a, trans_b, inject, report,
-             tier):
-    from . import choose_tier_grouped, ft_sgemm_grouped, grouped_layout
+             tier, streamk):
+    from . import (choose_tier_grouped, ft_sgemm_grouped, grouped_layout,
+                   grouped_streamk_gate)
+    from .ragged_streamk import has_streamk
+    shapes = grouped_layout(a_list, b_list, c_list, trans_a, trans_b)
     if tier is None:
-        tier = choose_tier_grouped(
-            grouped_layout(a_list, b_list, c_list, trans_a, trans_b))
+        tier = choose_tier_grouped(shapes)
+    # stream-K at the device grid: "always" wherever the tier has a twin and
+    # the group has units, True where the gate says so
+    has_units = any(s[0] > 0 and s[1] > 0 for s in shapes)
+    sk = has_streamk(tier) and has_units and (
+        streamk == "always" or
+        (streamk is True and grouped_streamk_gate(tier, shapes, True)))
     ft_sgemm_grouped(tier, a_list, b_list, c_list, 1.0, beta, inject=inject,
-                     report=report, trans_a=trans_a, trans_b=trans_b)
+                     report=report, trans_a=trans_a, trans_b=trans_b,
+                     streamk="auto" if sk else 0)
 
 
 class _FTGroupedLinearFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, bias, counts, inject, report, tier):
+    def forward(ctx, x, weight, bias, counts, inject, report, tier, streamk):
         x2 = _rows(x)
         w = weight if weight.stride(2) == 1 and \
             weight.stride(1) >= weight.shape[2] else weight.contiguous()
@@ -121,15 +130,15 @@ class _FTGroupedLinearFn(torch.autograd.Function):
             y = torch.empty((tokens, out), dtype=x.dtype, device=x.device)
         _product(list(w.unbind(0)), _split(x2, counts), _split(y, counts),
                  0.0 if bias is None else 1.0, True, True, inject, report,
-                 tier)
+                 tier, streamk)
         ctx.save_for_backward(x2, w, ids)
-        ctx.cfg = (counts, inject, report, tier)
+        ctx.cfg = (counts, inject, report, tier, streamk)
         return y
 
     @staticmethod
     def backward(ctx, grad_y):
         x2, w, ids = ctx.saved_tensors
-        counts, inject, report, tier = ctx.cfg
+        counts, inject, report, tier, streamk = ctx.cfg
         g = _rows(grad_y)
         g_list = _split(g, counts)
         grad_x = grad_w = grad_b = None
@@ -137,22 +146,23 @@ class _FTGroupedLinearFn(torch.autograd.Function):
             grad_x = torch.empty_like(x2,
                                       memory_format=torch.contiguous_format)
             _product(list(w.unbind(0)), g_list, _split(grad_x, counts), 0.0,
-                     False, True, inject, report, tier)
+                     False, True, inject, report, tier, streamk)
         if ctx.needs_input_grad[1]:
             grad_w = torch.empty_like(w, memory_format=torch.contiguous_format)
             _product(_split(x2, counts), g_list, list(grad_w.unbind(0)), 0.0,
-                     False, False, inject, report, tier)
+                     False, False, inject, report, tier, streamk)
         if ids is not None and ctx.needs_input_grad[2]:
             grad_b = torch.zeros((len(counts), g.shape[1]), dtype=g.dtype,
                                  device=g.device).index_add_(0, ids, g)
-        return grad_x, grad_w, grad_b, None, None, None, None
+        return grad_x, grad_w, grad_b, None, None, None, None, None
 
 
 def ft_grouped_linear(x: torch.Tensor, weight: torch.Tensor, counts,
                       bias: torch.Tensor | None = None, *,
                       inject: bool = False,
                       report: BatchedFaultReport | None = None,
-                      tier: str | None = None) -> torch.Tensor:
+                      tier: str | None = None,
+                      streamk=False) -> torch.Tensor:
     """y[rows of expert e] = x[rows of e] @ weight[e]^T + bias[e] on the
     grouped fused-ABFT SGEMM, differentiable.
 
@@ -175,7 +185,18 @@ def ft_grouped_linear(x: torch.Tensor, weight: torch.Tensor, counts,
     report: one BatchedFaultReport of E entries that accumulates over all
     products; expert e reports into slot e.
     tier: a tier name for every product; None picks choose_tier_grouped per
-    product."""
+    product.
+    streamk: False (the default) runs every product as the classic grouped
+    launch.  True lets each of the three products take the grouped stream-K
+    launch at the device grid where ops.grouped_streamk_gate says it is
+    expected to win (GROUPED_STREAMK_NOTE; the candidate is grad_weight,
+    whose K is the experts' token counts).  "always" takes it on every
+    product whose tier has a stream-K twin (large, huge), whatever the gate
+    says.  Split tiles then differ from the classic launch in summation
+    order only."""
+    if streamk not in (False, True, "always"):
+        raise ValueError(f"ft_grouped_linear: streamk must be False, True or "
+                         f"'always', got {streamk!r}")
     counts = _check(x, weight, counts, bias)
     return _FTGroupedLinearFn.apply(x, weight, bias, counts, inject, report,
-                                    tier)
+                                    tier, streamk)
